@@ -9,6 +9,15 @@ scaling, no data crosses xGMI) and the per-chunk digests are all-gathered over
 RCCL inside the timed step.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload config3]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.
+--dump-outputs DIR also writes what the last timed step computed (the arrays
+the caller of the timed path receives) as DIR/<name>.npy in float64; the
+inputs are seeded, so two builds can be compared output for output.  --full
+adds everything measured or checked beside the headline: the CPU baseline,
+the oracle's parity checks, the sustained-rate leg and each workload's
+side measurements (warm / graph forms, writer, NOTBATCHED, end to end).
 
 Other BASELINE configs (parity/measurement runs, same JSON shape):
   config2  1,048,576 x 64 B records (64 MiB): `value` is the cold rate (32
@@ -302,6 +311,26 @@ def read_ceiling(buf: torch.Tensor, nbytes: int, stream) -> float:
     return best
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(args, world: int, rank: int, arrays: dict) -> None:
+    """--dump-outputs DIR: what the last timed step computed, one
+    DIR/<name>.npy per array in float64 (exact for the 32-bit CRCs and the
+    counts), at most 64 MB in all; with N > 1 ranks every rank writes its own
+    shard's arrays as <name>_rank<r>.npy."""
+    if not args.dump_outputs:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes of outputs")
+        np.save(os.path.join(args.dump_outputs, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
 class Timer:
     """K timed steps bracketed by barrier + synchronize; max over ranks.
 
@@ -351,6 +380,7 @@ def line(args, world, elapsed, total_bytes, config, roofline, scaling="weak", da
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": scaling,
@@ -409,7 +439,9 @@ def run_config3(args, world, rank, dev, stream):
     # settling after idle (~20-30 ms, longer than 5 warmup steps) would
     # otherwise land in the timed steps (DESIGN_LOG.md 1.6,
     # profiles/r02/sustain*.jsonl); the streaming probe brings the package to
-    # its loaded operating point as a sustained checksum job finds it.
+    # its loaded operating point as a sustained checksum job finds it.  The
+    # headline needs that settling, so a plain run keeps the probe (26 reads
+    # of the batch, ~20 ms) and reports the ceiling it measured.
     read_peak = read_ceiling(data, NCHUNK * CHUNK, stream)
     tm = Timer(world, dev, stream)
     elapsed = tm.run(step, args.steps, args.warmup)
@@ -421,28 +453,34 @@ def run_config3(args, world, rank, dev, stream):
         dist.all_gather_into_tensor(gathered, out)
         torch.cuda.synchronize()
         assert torch.equal(gathered[rank * NCHUNK:(rank + 1) * NCHUNK], out)
-    # after the timed region, reported beside it (never the value): the
-    # kernel over 200 back-to-back calls, the sustained power-capped rate
-    sus = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(200)]
-    for a, b in sus:
-        a.record(stream)
-        check(lib().zscrc_device_fixed(data.data_ptr(), CHUNK, CHUNK, 0, out.data_ptr(), NCHUNK, 0,
-                                       stream.cuda_stream), "zscrc_device_fixed")
-        b.record(stream)
-    torch.cuda.synchronize()
-    sus_ms = sorted(a.elapsed_time(b) for a, b in sus)
-    sustained = {"kernel_ms_median": round(sus_ms[len(sus_ms) // 2], 4),
-                 "kernel_ms_mean": round(float(np.mean(sus_ms)), 4), "calls": len(sus_ms),
-                 "note": "200 back-to-back calls after the timed steps (the package at its 1400 W cap; "
-                         "DESIGN_LOG.md 1.6); reported only"}
-    # the timed call's own outputs: 256 sampled chunks against the oracle
-    torch.cuda.synchronize()
-    host_out = out.cpu().numpy().view(np.uint32)
-    idx = np.unique(np.concatenate([[0, NCHUNK - 1],
-                                    np.random.default_rng(rank).integers(0, NCHUNK, 254)]))
-    n_bad = spot_check(host_out, data, idx, CHUNK, CHUNK)
-    if n_bad:
-        raise SystemExit(f"config3: {n_bad} of {idx.size} sampled chunk CRCs differ from the oracle")
+    if args.dump_outputs:
+        dump_outputs(args, world, rank, {"crc": out.cpu().numpy().view(np.uint32)})
+    extra = {}
+    if args.full:
+        # after the timed region, reported beside it (never the value): the
+        # kernel over 200 back-to-back calls, the sustained power-capped rate
+        sus = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(200)]
+        for a, b in sus:
+            a.record(stream)
+            check(lib().zscrc_device_fixed(data.data_ptr(), CHUNK, CHUNK, 0, out.data_ptr(), NCHUNK, 0,
+                                           stream.cuda_stream), "zscrc_device_fixed")
+            b.record(stream)
+        torch.cuda.synchronize()
+        sus_ms = sorted(a.elapsed_time(b) for a, b in sus)
+        sustained = {"kernel_ms_median": round(sus_ms[len(sus_ms) // 2], 4),
+                     "kernel_ms_mean": round(float(np.mean(sus_ms)), 4), "calls": len(sus_ms),
+                     "note": "200 back-to-back calls after the timed steps (the package at its 1400 W cap; "
+                             "DESIGN_LOG.md 1.6); reported only"}
+        # the timed call's own outputs: 256 sampled chunks against the oracle
+        torch.cuda.synchronize()
+        host_out = out.cpu().numpy().view(np.uint32)
+        idx = np.unique(np.concatenate([[0, NCHUNK - 1],
+                                        np.random.default_rng(rank).integers(0, NCHUNK, 254)]))
+        n_bad = spot_check(host_out, data, idx, CHUNK, CHUNK)
+        if n_bad:
+            raise SystemExit(f"config3: {n_bad} of {idx.size} sampled chunk CRCs differ from the oracle")
+        extra = {"parity": {"sampled_chunks": int(idx.size), "mismatches": n_bad, "checker": "oracle crc32c_hw"},
+                 "sustained": sustained}
     kname = "zs::" + lib().zscrc_fixed_kernel(data.data_ptr(), CHUNK, CHUNK, NCHUNK).decode()
     r = roof(NCHUNK * CHUNK + NCHUNK * 4, kern_ms, kname, "config3", read_peak)
     out_line = line(args, world, elapsed, NCHUNK * CHUNK * world * args.steps,
@@ -450,9 +488,8 @@ def run_config3(args, world, rank, dev, stream):
                      "records_per_gpu": NCHUNK, "record_bytes": CHUNK,
                      "parallelism": f"shard{world}" + ("; digests gathered once after the timed steps "
                                                        f"({os.environ.get('BENCH_DIST', 'nccl')})" if world > 1 else "")}, r,
-                    parity={"sampled_chunks": int(idx.size), "mismatches": n_bad, "checker": "oracle crc32c_hw"},
-                    sustained=sustained)
-    if rank == 0 and world == 1 and not args.no_cpu:
+                    **extra)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # 8,192 of the timed chunks (512 MiB: beyond the host's L3)
         ns = 8192
         out_line["cpu_baseline"] = cpu_leg(data[:ns * CHUNK].cpu().numpy(), f"{ns} x 64 KiB chunks of the workload",
@@ -520,21 +557,38 @@ def run_config2(args, world, rank, dev, stream):
 
     read_peak = read_ceiling(bufs.view(-1), bufs.numel(), stream)   # also settles power (run_config3)
     tm = Timer(world, dev, stream)
-    warm_el = tm.run(multi(warm_bufs), replays, max(1, args.warmup // rot + 1))
-    warm_ms = float(np.median(tm.kern_ms)) / rot
+    if args.full:
+        warm_el = tm.run(multi(warm_bufs), replays, max(1, args.warmup // rot + 1))
+        warm_ms = float(np.median(tm.kern_ms)) / rot
     elapsed = tm.run(multi(cold_bufs), replays, max(1, args.warmup // rot + 1))
     cold_ms = float(np.mean(tm.kern_ms)) / rot
-    # every batch of the last multi launch against plain single-batch launches
-    for k in (0, rot // 2, rot - 1):
-        ref = torch.empty(n, dtype=torch.int32, device=dev)
-        launch(bufs[k], ref, stream)
-        torch.cuda.synchronize(dev)
-        assert torch.equal(ref, outs[k]), f"multi-batch result of batch {k} differs from a direct launch"
-    g_cold = capture(lambda k: k)
-    tm_g = Timer(world, dev, stream)
-    graph_el = tm_g.run(stepper(g_cold), replays, 1)
-    graph_ms = float(np.mean(tm_g.kern_ms)) / rot
+    if args.dump_outputs:
+        # the last launch's CRCs of all 64 batches (256 MB): a fixed, seeded
+        # sample of 2^20 of them, with the positions sampled
+        pick = np.sort(np.random.default_rng(0x64).choice(rot * n, 1 << 20, replace=False))
+        got = outs.view(-1)[torch.from_numpy(pick).to(dev)].cpu().numpy().view(np.uint32)
+        dump_outputs(args, world, rank, {"crc_sample": got, "crc_sample_index": pick})
     nbytes = n * rl + n * 4
+    extra = {}
+    if args.full:
+        # every batch of the last multi launch against plain single-batch launches
+        for k in (0, rot // 2, rot - 1):
+            ref = torch.empty(n, dtype=torch.int32, device=dev)
+            launch(bufs[k], ref, stream)
+            torch.cuda.synchronize(dev)
+            assert torch.equal(ref, outs[k]), f"multi-batch result of batch {k} differs from a direct launch"
+        g_cold = capture(lambda k: k)
+        tm_g = Timer(world, dev, stream)
+        graph_el = tm_g.run(stepper(g_cold), replays, 1)
+        graph_ms = float(np.mean(tm_g.kern_ms)) / rot
+        extra = {"warm": {"value": round(n * rl * world * steps / warm_el / GIB, 2), "kernel_ms": round(warm_ms, 4),
+                          "achieved_GBs": round(nbytes / (warm_ms * 1e-3) / 1e9, 1),
+                          "note": "one batch re-read every step: L3 (Infinity Cache) resident"},
+                 "graph_of_launches": {"value": round(n * rl * world * steps / graph_el / GIB, 2),
+                                       "kernel_ms": round(graph_ms, 4),
+                                       "achieved_GBs": round(nbytes / (graph_ms * 1e-3) / 1e9, 1),
+                                       "note": f"round-1 form: {rot} single-batch short_kernel launches per "
+                                               "hipGraph"}}
     r = roof(nbytes, cold_ms, "zs::multi64_kernel", "config2", read_peak,
              f"{rot} batches of 1M x 64 B per launch; kernel_ms = launch time / {rot} batches (the algorithmic "
              "bytes and the traffic are per batch)")
@@ -543,18 +597,10 @@ def run_config2(args, world, rank, dev, stream):
                                  f"rotating batches ({rot * n * rl >> 30} GiB); {rot} steps per "
                                  "zscrc_device_fixed_multi launch",
                      "records_per_gpu": n, "record_bytes": rl, "parallelism": f"shard{world}"}, r,
-                    warm={"value": round(n * rl * world * steps / warm_el / GIB, 2), "kernel_ms": round(warm_ms, 4),
-                          "achieved_GBs": round(nbytes / (warm_ms * 1e-3) / 1e9, 1),
-                          "note": "one batch re-read every step: L3 (Infinity Cache) resident"},
-                    graph_of_launches={"value": round(n * rl * world * steps / graph_el / GIB, 2),
-                                       "kernel_ms": round(graph_ms, 4),
-                                       "achieved_GBs": round(nbytes / (graph_ms * 1e-3) / 1e9, 1),
-                                       "note": f"round-1 form: {rot} single-batch short_kernel launches per "
-                                               "hipGraph"},
                     amortized=(f"value is amortized over {rot} batches per zscrc_device_fixed_multi launch (launch "
                                "cost, LDS table fill and HBM ramp paid once per launch); the per-batch launch "
-                               "form is graph_of_launches"))
-    if rank == 0 and world == 1 and not args.no_cpu:
+                               "form is graph_of_launches (--full)"), **extra)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # 8 of the cold batches (8 M records, 512 MiB: beyond the host's L3)
         h = bufs[:8].cpu().numpy().reshape(-1)
         out_line["cpu_baseline"] = cpu_leg(h, "8 batches of 1,048,576 x 64 B records", n=8 * n, stride=rl,
@@ -645,188 +691,216 @@ def run_config4(args, world, rank, dev, stream):
     stale = torch.nonzero(lens == 0).flatten()
     bad = torch.sort(vout[1][:nbad]).values
     assert nbad == nfiles and torch.equal(bad, stale), (nbad, nfiles)
+    if args.dump_outputs:
+        dump_outputs(args, world, rank, {"bad_count": np.array([nbad]), "bad_commits": bad.cpu().numpy()})
 
-    # per-commit crc + status arrays (zscrc_device_verify_commits_bounded)
-    res = {}
+    nbytes = span_bytes + 8 * ncommit + 16 * ncommit   # spans + commit trailers + descriptors
+    extra = {}
+    if args.full:
+        # per-commit crc + status arrays (zscrc_device_verify_commits_bounded)
+        res = {}
 
-    def arrays():
-        res["crc"], res["st"] = zsfile.verify_commits(flat, offs, lens, max_len=max_span)
-    arrays_ms = _timed(arrays, 10, stream)
-    st = res["st"]
-    n_ok = int((st == 1).sum().item())
-    assert n_ok + nfiles == ncommit
+        def arrays():
+            res["crc"], res["st"] = zsfile.verify_commits(flat, offs, lens, max_len=max_span)
+        arrays_ms = _timed(arrays, 10, stream)
+        st = res["st"]
+        n_ok = int((st == 1).sum().item())
+        assert n_ok + nfiles == ncommit
 
-    # writer side: recompute + store every commit CRC (the image is unchanged;
-    # the stale finalise commits are not rewritten)
-    offs_w, lens_w = offs[lens > 0].contiguous(), lens[lens > 0].contiguous()
-    write_ms = _timed(lambda: zsfile.write_commits(flat, offs_w, lens_w, max_len=max_span, crc=False), 6, stream)
-    write_crc_ms = _timed(lambda: zsfile.write_commits(flat, offs_w, lens_w, max_len=max_span), 6, stream)
-    # the writer's CRCs out of place (commit mode 3): the kernel of the
-    # host-image writer below -- 4 coalesced bytes per commit, no in-place store
-    crcs_ms = _timed(lambda: zsfile.commit_crcs(flat, offs_w, lens_w, max_len=max_span), 10, stream)
-    want_w = res["crc"][lens > 0]
-    assert torch.equal(zsfile.commit_crcs(flat, offs_w, lens_w, max_len=max_span), want_w)
+        # writer side: recompute + store every commit CRC (the image is unchanged;
+        # the stale finalise commits are not rewritten)
+        offs_w, lens_w = offs[lens > 0].contiguous(), lens[lens > 0].contiguous()
+        write_ms = _timed(lambda: zsfile.write_commits(flat, offs_w, lens_w, max_len=max_span, crc=False), 6, stream)
+        write_crc_ms = _timed(lambda: zsfile.write_commits(flat, offs_w, lens_w, max_len=max_span), 6, stream)
+        # the writer's CRCs out of place (commit mode 3): the kernel of the
+        # host-image writer below -- 4 coalesced bytes per commit, no in-place store
+        crcs_ms = _timed(lambda: zsfile.commit_crcs(flat, offs_w, lens_w, max_len=max_span), 10, stream)
+        want_w = res["crc"][lens > 0]
+        assert torch.equal(zsfile.commit_crcs(flat, offs_w, lens_w, max_len=max_span), want_w)
 
-    # NOTBATCHED (zsbench writeseq): one commit per ~2 MiB file, unbounded
-    # (device length classes; the spans go to xteam_kernel's parts mode)
-    ppf_nb = zg.pairs_per_file(False)
-    nf_nb = -(-pairs_total // ppf_nb)
-    img_nb = zg.log_files(uuid, 0, nf_nb, ppf_nb, 0, False, gen, dev, batched=False)
-    o_nb, l_nb = zg.log_spans(nf_nb, ppf_nb, False, False, dev)
-    nbo = (torch.empty(1, dtype=torch.int64, device=dev), torch.empty(64, dtype=torch.int64, device=dev))
-    # the walk knows the commits' length range: classes outside it get no
-    # launch (zscrc_device_verify_commits_verdict_range)
-    nb_lo, nb_hi = int(l_nb.min().item()), int(l_nb.max().item())
-    nb_arr = {}
+        # NOTBATCHED (zsbench writeseq): one commit per ~2 MiB file, unbounded
+        # (device length classes; the spans go to xteam_kernel's parts mode)
+        ppf_nb = zg.pairs_per_file(False)
+        nf_nb = -(-pairs_total // ppf_nb)
+        img_nb = zg.log_files(uuid, 0, nf_nb, ppf_nb, 0, False, gen, dev, batched=False)
+        o_nb, l_nb = zg.log_spans(nf_nb, ppf_nb, False, False, dev)
+        nbo = (torch.empty(1, dtype=torch.int64, device=dev), torch.empty(64, dtype=torch.int64, device=dev))
+        # the walk knows the commits' length range: classes outside it get no
+        # launch (zscrc_device_verify_commits_verdict_range)
+        nb_lo, nb_hi = int(l_nb.min().item()), int(l_nb.max().item())
+        nb_arr = {}
 
-    def nb_verdict():
-        zsfile.verify_commits_verdict(img_nb.view(-1), o_nb, l_nb, out=nbo, min_len=nb_lo, max_len=nb_hi)
+        def nb_verdict():
+            zsfile.verify_commits_verdict(img_nb.view(-1), o_nb, l_nb, out=nbo, min_len=nb_lo, max_len=nb_hi)
 
-    def nb_verdict_unranged():
-        zsfile.verify_commits_verdict(img_nb.view(-1), o_nb, l_nb, out=nbo)
+        def nb_verdict_unranged():
+            zsfile.verify_commits_verdict(img_nb.view(-1), o_nb, l_nb, out=nbo)
 
-    def nb_arrays():
-        nb_arr["crc"], nb_arr["st"] = zsfile.verify_commits(img_nb.view(-1), o_nb, l_nb)
-    # interleaved, so no form sees a different power / clock state; blocks of
-    # 20 calls (6 could not resolve the forms' ~13 us difference,
-    # tools/probes/nb_forms.py)
-    nb_ms, nb_unranged_ms, nb_arrays_ms = _timed_ab([nb_verdict, nb_verdict_unranged, nb_arrays], 20, stream,
-                                                    rounds=5)
-    nb_verdict()
-    assert int(nbo[0].item()) == 0
-    assert bool((nb_arr["st"] == 1).all())
-    nb_bytes = int(l_nb.sum().item()) + 24 * nf_nb
-    # the checker on the NOTBATCHED image: every ~2 MiB commit against the oracle
-    nb_parity = oracle_check_logs(img_nb.cpu().numpy(), o_nb.cpu().numpy(), l_nb.cpu().numpy(),
-                                  nb_arr["crc"].cpu().numpy().view(np.uint32), 0)
-    assert nb_parity["mismatches"] == 0, nb_parity
-    del img_nb
+        def nb_arrays():
+            nb_arr["crc"], nb_arr["st"] = zsfile.verify_commits(img_nb.view(-1), o_nb, l_nb)
+        # interleaved, so no form sees a different power / clock state; blocks of
+        # 20 calls (6 could not resolve the forms' ~13 us difference,
+        # tools/probes/nb_forms.py)
+        nb_ms, nb_unranged_ms, nb_arrays_ms = _timed_ab([nb_verdict, nb_verdict_unranged, nb_arrays], 20, stream,
+                                                        rounds=5)
+        nb_verdict()
+        assert int(nbo[0].item()) == 0
+        assert bool((nb_arr["st"] == 1).all())
+        nb_bytes = int(l_nb.sum().item()) + 24 * nf_nb
+        # the checker on the NOTBATCHED image: every ~2 MiB commit against the oracle
+        nb_parity = oracle_check_logs(img_nb.cpu().numpy(), o_nb.cpu().numpy(), l_nb.cpu().numpy(),
+                                      nb_arr["crc"].cpu().numpy().view(np.uint32), 0)
+        assert nb_parity["mismatches"] == 0, nb_parity
+        del img_nb
 
-    # the checker at full size: every file walked and every commit CRC
-    # recomputed by the CPU oracle, the GPU's crc array compared
-    host = img.cpu()
-    parity = oracle_check_logs(host.numpy(), offs.cpu().numpy(), lens.cpu().numpy(),
-                               res["crc"].cpu().numpy().view(np.uint32), 1)
-    parity["notbatched"] = nb_parity
-    if parity["mismatches"] or parity["commits_walked"] != ncommit:
-        raise SystemExit(f"config4: the oracle disagrees with the GPU: {parity}")
+        # the checker at full size: every file walked and every commit CRC
+        # recomputed by the CPU oracle, the GPU's crc array compared
+        host = img.cpu()
+        parity = oracle_check_logs(host.numpy(), offs.cpu().numpy(), lens.cpu().numpy(),
+                                   res["crc"].cpu().numpy().view(np.uint32), 1)
+        parity["notbatched"] = nb_parity
+        if parity["mismatches"] or parity["commits_walked"] != ncommit:
+            raise SystemExit(f"config4: the oracle disagrees with the GPU: {parity}")
 
-    # end to end from host memory, both directions
-    e2e = {}
-    if rank == 0 and not args.no_e2e:
-        pinned = torch.empty(host.shape, dtype=torch.uint8, pin_memory=True)
-        pinned.copy_(host)
-        for kind, src in (("pageable", host), ("pinned", pinned)):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            img.copy_(src, non_blocking=True)
-            torch.cuda.synchronize()
-            e2e[f"h2d_{kind}_GBs"] = round(img.numel() / (time.perf_counter() - t0) / 1e9, 2)
-        # verify: zscrc_zs_verify_files over the host file images (threaded
-        # walks + pinned staging + overlapped H2D + one verify)
-        images = list(host.numpy().reshape(nfiles, -1))
-        kinds = [zsfile.FINALISED] * nfiles
-        zsfile.verify_files(images, kinds)                 # warm: pinned slots, device buffers
-        best = None
-        for _ in range(3):
-            t0 = time.perf_counter()
-            rep = zsfile.verify_files(images, kinds)
-            dt = time.perf_counter() - t0
-            best = dt if best is None or dt < best else best
-        assert rep["commits"] == ncommit and rep["bad_commits"] == 0, rep
-        e2e["verify_files_s"] = round(best, 4)
-        e2e["verify_files_GBs"] = round(host.numel() / best / 1e9, 2)
-        e2e["verify_files_phases_s"] = {"copy": round(rep["copy_s"], 4), "verify_tail": round(rep["verify_tail_s"], 4),
-                                        "total_in_library": round(rep["total_s"], 4)}
-        # write: host images -> H2D -> write_commits -> D2H of the images
-        back = torch.empty(host.shape, dtype=torch.uint8, pin_memory=True)
-        for kind, src, dst in (("pinned", pinned, back), ("pageable", host, torch.empty_like(host))):
+        # end to end from host memory, both directions
+        e2e = {}
+        if rank == 0 and not args.no_e2e:
+            pinned = torch.empty(host.shape, dtype=torch.uint8, pin_memory=True)
+            pinned.copy_(host)
+            for kind, src in (("pageable", host), ("pinned", pinned)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                img.copy_(src, non_blocking=True)
+                torch.cuda.synchronize()
+                e2e[f"h2d_{kind}_GBs"] = round(img.numel() / (time.perf_counter() - t0) / 1e9, 2)
+            # verify: zscrc_zs_verify_files over the host file images (threaded
+            # walks + pinned staging + overlapped H2D + one verify)
+            images = list(host.numpy().reshape(nfiles, -1))
+            kinds = [zsfile.FINALISED] * nfiles
+            zsfile.verify_files(images, kinds)                 # warm: pinned slots, device buffers
+            best = None
+            for _ in range(3):
+                t0 = time.perf_counter()
+                rep = zsfile.verify_files(images, kinds)
+                dt = time.perf_counter() - t0
+                best = dt if best is None or dt < best else best
+            assert rep["commits"] == ncommit and rep["bad_commits"] == 0, rep
+            e2e["verify_files_s"] = round(best, 4)
+            e2e["verify_files_GBs"] = round(host.numel() / best / 1e9, 2)
+            e2e["verify_files_phases_s"] = {"copy": round(rep["copy_s"], 4),
+                                            "verify_tail": round(rep["verify_tail_s"], 4),
+                                            "total_in_library": round(rep["total_s"], 4)}
+            # write: host images -> H2D -> write_commits -> D2H of the images
+            back = torch.empty(host.shape, dtype=torch.uint8, pin_memory=True)
+            for kind, src, dst in (("pinned", pinned, back), ("pageable", host, torch.empty_like(host))):
+                ts = []
+                for _ in range(3):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    img.copy_(src, non_blocking=True)
+                    zsfile.write_commits(flat, offs_w, lens_w, max_len=max_span, crc=False)
+                    dst.copy_(img, non_blocking=True)
+                    torch.cuda.synchronize()
+                    ts.append(time.perf_counter() - t0)
+                e2e[f"write_{kind}_s"] = round(min(ts), 4)
+                e2e[f"write_{kind}_GBs"] = round(host.numel() / min(ts) / 1e9, 2)
+            assert torch.equal(back, pinned)
+            # the write pipelined: file-aligned chunks, H2D / writer / D2H each on
+            # its own stream, so the two copy directions (PCIe is full duplex)
+            # and the kernel overlap chunk by chunk
+            fsz = flat.numel() // nfiles
+            per = 64
+            ow_h, lw_h = offs_w.cpu(), lens_w.cpu()
+            chunks = []
+            for f0 in range(0, nfiles, per):
+                c0, c1 = f0 * fsz, min(nfiles, f0 + per) * fsz
+                sel = (ow_h >= c0) & (ow_h < c1)
+                chunks.append((c0, c1, (ow_h[sel] - c0).to(dev), lw_h[sel].to(dev)))
+            assert sum(int(c[2].numel()) for c in chunks) == int(offs_w.numel())
+            s_in, s_k, s_out = (torch.cuda.Stream(dev) for _ in range(3))
+            src_f, dst_f = pinned.view(-1), back.view(-1)
+
+            def pipelined():
+                for c0, c1, o, ln in chunks:
+                    with torch.cuda.stream(s_in):
+                        flat[c0:c1].copy_(src_f[c0:c1], non_blocking=True)
+                        e_in = torch.cuda.Event()
+                        e_in.record(s_in)
+                    s_k.wait_event(e_in)
+                    with torch.cuda.stream(s_k):
+                        zsfile.write_commits(flat[c0:c1], o, ln, max_len=max_span, crc=False)
+                        e_k = torch.cuda.Event()
+                        e_k.record(s_k)
+                    s_out.wait_event(e_k)
+                    with torch.cuda.stream(s_out):
+                        dst_f[c0:c1].copy_(flat[c0:c1], non_blocking=True)
+                torch.cuda.synchronize()
+            back.zero_()
             ts = []
             for _ in range(3):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                img.copy_(src, non_blocking=True)
-                zsfile.write_commits(flat, offs_w, lens_w, max_len=max_span, crc=False)
-                dst.copy_(img, non_blocking=True)
-                torch.cuda.synchronize()
+                pipelined()
                 ts.append(time.perf_counter() - t0)
-            e2e[f"write_{kind}_s"] = round(min(ts), 4)
-            e2e[f"write_{kind}_GBs"] = round(host.numel() / min(ts) / 1e9, 2)
-        assert torch.equal(back, pinned)
-        # the write pipelined: file-aligned chunks, H2D / writer / D2H each on
-        # its own stream, so the two copy directions (PCIe is full duplex)
-        # and the kernel overlap chunk by chunk
-        fsz = flat.numel() // nfiles
-        per = 64
-        ow_h, lw_h = offs_w.cpu(), lens_w.cpu()
-        chunks = []
-        for f0 in range(0, nfiles, per):
-            c0, c1 = f0 * fsz, min(nfiles, f0 + per) * fsz
-            sel = (ow_h >= c0) & (ow_h < c1)
-            chunks.append((c0, c1, (ow_h[sel] - c0).to(dev), lw_h[sel].to(dev)))
-        assert sum(int(c[2].numel()) for c in chunks) == int(offs_w.numel())
-        s_in, s_k, s_out = (torch.cuda.Stream(dev) for _ in range(3))
-        src_f, dst_f = pinned.view(-1), back.view(-1)
-
-        def pipelined():
-            for c0, c1, o, ln in chunks:
-                with torch.cuda.stream(s_in):
-                    flat[c0:c1].copy_(src_f[c0:c1], non_blocking=True)
-                    e_in = torch.cuda.Event()
-                    e_in.record(s_in)
-                s_k.wait_event(e_in)
-                with torch.cuda.stream(s_k):
-                    zsfile.write_commits(flat[c0:c1], o, ln, max_len=max_span, crc=False)
-                    e_k = torch.cuda.Event()
-                    e_k.record(s_k)
-                s_out.wait_event(e_k)
-                with torch.cuda.stream(s_out):
-                    dst_f[c0:c1].copy_(flat[c0:c1], non_blocking=True)
-            torch.cuda.synchronize()
-        back.zero_()
-        ts = []
-        for _ in range(3):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            pipelined()
-            ts.append(time.perf_counter() - t0)
-        assert torch.equal(back, pinned)
-        e2e["write_pipelined_s"] = round(min(ts), 4)
-        e2e["write_pipelined_GBs"] = round(host.numel() / min(ts) / 1e9, 2)
-        # the writer for a host image, CRCs back (zscrc_zs_fill_commits):
-        # image H2D in chunks, commit mode 3, 4 B per commit D2H, host threads
-        # patch the CRC fields -- the reference writer builds its commit
-        # records on the host (src/zeroskip-file.c:315-331).  The fields are
-        # zeroed first, so the first call is checked byte for byte.
-        ow_np = offs_w.cpu().numpy().astype(np.uint64)
-        lw_np = lens_w.cpu().numpy().astype(np.uint64)
-        fields = (ow_np + lw_np + 4).astype(np.int64)[:, None] + np.arange(4, dtype=np.int64)
-        for kind, buf in (("pinned", pinned.view(-1)), ("pageable", host.view(-1).clone())):
-            arr = buf.numpy()
-            arr[fields] = 0
-            zsfile.fill_commits(buf, ow_np, lw_np, max_len=max_span)
-            assert torch.equal(buf, host.view(-1)), f"fill_commits ({kind}) differs from the GPU-written image"
-            ts, rep_f = [], None
-            for _ in range(3):
-                t0 = time.perf_counter()
-                rep_f = zsfile.fill_commits(buf, ow_np, lw_np, max_len=max_span)
-                ts.append(time.perf_counter() - t0)
-            e2e[f"write_crcs_{kind}_s"] = round(min(ts), 4)
-            e2e[f"write_crcs_{kind}_GBs"] = round(host.numel() / min(ts) / 1e9, 2)
-            e2e[f"write_crcs_{kind}_phases_s"] = {"setup": round(rep_f["setup_s"], 5), "h2d": round(rep_f["h2d_s"], 4),
-                                                  "total": round(rep_f["total_s"], 4),
-                                                  "chunks": rep_f["chunks"], "threads": rep_f["threads"]}
-            del buf, arr
-        e2e["write_crcs_pipelined_GBs"] = e2e["write_crcs_pinned_GBs"]
-        e2e["note"] = ("verify: host file images -> verdicts, walks included (zscrc_zs_verify_files, "
-                       f"{rep['threads']} host threads); write: host images -> H2D -> GPU commit writer -> "
-                       "D2H of the images (image bytes / wall time), whole image at once or pipelined in "
-                       f"{len(chunks)} file-aligned chunks on three streams; write_crcs: host image -> H2D chunks "
-                       "-> commit CRCs out of place -> 4 B per commit D2H -> host threads patch the image "
-                       "(zscrc_zs_fill_commits); PCIe-bound, never the line's value")
-        del images, pinned, back
-
-    nbytes = span_bytes + 8 * ncommit + 16 * ncommit   # spans + commit trailers + descriptors
+            assert torch.equal(back, pinned)
+            e2e["write_pipelined_s"] = round(min(ts), 4)
+            e2e["write_pipelined_GBs"] = round(host.numel() / min(ts) / 1e9, 2)
+            # the writer for a host image, CRCs back (zscrc_zs_fill_commits):
+            # image H2D in chunks, commit mode 3, 4 B per commit D2H, host threads
+            # patch the CRC fields -- the reference writer builds its commit
+            # records on the host (src/zeroskip-file.c:315-331).  The fields are
+            # zeroed first, so the first call is checked byte for byte.
+            ow_np = offs_w.cpu().numpy().astype(np.uint64)
+            lw_np = lens_w.cpu().numpy().astype(np.uint64)
+            fields = (ow_np + lw_np + 4).astype(np.int64)[:, None] + np.arange(4, dtype=np.int64)
+            for kind, buf in (("pinned", pinned.view(-1)), ("pageable", host.view(-1).clone())):
+                arr = buf.numpy()
+                arr[fields] = 0
+                zsfile.fill_commits(buf, ow_np, lw_np, max_len=max_span)
+                assert torch.equal(buf, host.view(-1)), f"fill_commits ({kind}) differs from the GPU-written image"
+                ts, rep_f = [], None
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    rep_f = zsfile.fill_commits(buf, ow_np, lw_np, max_len=max_span)
+                    ts.append(time.perf_counter() - t0)
+                e2e[f"write_crcs_{kind}_s"] = round(min(ts), 4)
+                e2e[f"write_crcs_{kind}_GBs"] = round(host.numel() / min(ts) / 1e9, 2)
+                e2e[f"write_crcs_{kind}_phases_s"] = {"setup": round(rep_f["setup_s"], 5),
+                                                      "h2d": round(rep_f["h2d_s"], 4),
+                                                      "total": round(rep_f["total_s"], 4),
+                                                      "chunks": rep_f["chunks"], "threads": rep_f["threads"]}
+                del buf, arr
+            e2e["write_crcs_pipelined_GBs"] = e2e["write_crcs_pinned_GBs"]
+            e2e["note"] = ("verify: host file images -> verdicts, walks included (zscrc_zs_verify_files, "
+                           f"{rep['threads']} host threads); write: host images -> H2D -> GPU commit writer -> "
+                           "D2H of the images (image bytes / wall time), whole image at once or pipelined in "
+                           f"{len(chunks)} file-aligned chunks on three streams; write_crcs: host image -> H2D chunks "
+                           "-> commit CRCs out of place -> 4 B per commit D2H -> host threads patch the image "
+                           "(zscrc_zs_fill_commits); PCIe-bound, never the line's value")
+            del images, pinned, back
+        extra = {"parity": parity,
+                 "per_commit_arrays": {"ms": round(arrays_ms, 4),
+                                       "GBs": round((nbytes + 8 * ncommit) / (arrays_ms * 1e-3) / 1e9, 1),
+                                       "note": "zscrc_device_verify_commits_bounded: crc + status per commit "
+                                               "(8 B of HBM writes per commit)"},
+                 "write": {"ms": round(write_ms, 4),
+                           "GBs": round((span_bytes + 8 * ncommit) / (write_ms * 1e-3) / 1e9, 1),
+                           "ms_with_crc_array": round(write_crc_ms, 4),
+                           "crc_array_ms": round(crcs_ms, 4),
+                           "crc_array_GBs": round((span_bytes + 8 * ncommit + 16 * ncommit + 4 * ncommit) /
+                                                  (crcs_ms * 1e-3) / 1e9, 1),
+                           "note": "ms: zscrc_device_write_commits_bounded, CRCs into the image (d_crc NULL); "
+                                   "crc_array_ms: zscrc_device_commit_crcs_bounded, the writer's CRCs to a "
+                                   "coalesced 4 B array, image untouched (the kernel of write_crcs in e2e)"},
+                 "notbatched": {"files": nf_nb, "commits": nf_nb, "verify_ms": round(nb_ms, 4),
+                                 "GBs": round(nb_bytes / (nb_ms * 1e-3) / 1e9, 1),
+                                 "frac": round(nb_bytes / (nb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                 "verify_unranged_ms": round(nb_unranged_ms, 4),
+                                 "arrays_ms": round(nb_arrays_ms, 4),
+                                 "note": "verify_ms: the verdict with the walk's length range (min/max span), "
+                                         "unranged: without it, arrays: per-commit crc + status; the three "
+                                         "timed interleaved"},
+                 "e2e": e2e}
     r = roof(nbytes, kern_ms, "zs::commit_kernel<false, true, 1024>", "config4", read_peak,
              "verdict, the run-only form at 16 waves per CU: run rounds of 64 back-to-back spans as coalesced "
              "1 KiB loads, other rounds in one-piece quad bursts")
@@ -837,29 +911,9 @@ def run_config4(args, world, rank, dev, stream):
                      "files": nfiles, "commits": ncommit, "parallelism": f"replica{world}"},
                     r, data="synthetic zsbench records (key %016d, 255 charset chars + NUL, fixed seed), "
                             "byte-exact zeroskip log images in HBM",
-                    verdict={"bad_commits": nbad, "stale_finalise_commits": nfiles}, parity=parity,
-                    per_commit_arrays={"ms": round(arrays_ms, 4),
-                                       "GBs": round((nbytes + 8 * ncommit) / (arrays_ms * 1e-3) / 1e9, 1),
-                                       "note": "zscrc_device_verify_commits_bounded: crc + status per commit "
-                                               "(8 B of HBM writes per commit)"},
-                    write={"ms": round(write_ms, 4), "GBs": round((span_bytes + 8 * ncommit) / (write_ms * 1e-3) / 1e9, 1),
-                           "ms_with_crc_array": round(write_crc_ms, 4),
-                           "crc_array_ms": round(crcs_ms, 4),
-                           "crc_array_GBs": round((span_bytes + 8 * ncommit + 16 * ncommit + 4 * ncommit) /
-                                                  (crcs_ms * 1e-3) / 1e9, 1),
-                           "note": "ms: zscrc_device_write_commits_bounded, CRCs into the image (d_crc NULL); "
-                                   "crc_array_ms: zscrc_device_commit_crcs_bounded, the writer's CRCs to a "
-                                   "coalesced 4 B array, image untouched (the kernel of write_crcs in e2e)"},
-                    notbatched={"files": nf_nb, "commits": nf_nb, "verify_ms": round(nb_ms, 4),
-                                "GBs": round(nb_bytes / (nb_ms * 1e-3) / 1e9, 1),
-                                "frac": round(nb_bytes / (nb_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                "verify_unranged_ms": round(nb_unranged_ms, 4),
-                                "arrays_ms": round(nb_arrays_ms, 4),
-                                "note": "verify_ms: the verdict with the walk's length range (min/max span), "
-                                        "unranged: without it, arrays: per-commit crc + status; the three "
-                                        "timed interleaved"},
-                    e2e=e2e, gen_s=round(t_gen, 2))
-    if rank == 0 and world == 1 and not args.no_cpu:
+                    verdict={"bad_commits": nbad, "stale_finalise_commits": nfiles},
+                    gen_s=round(t_gen, 2), **extra)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # the first quarter of the replay's files (~2.5 M commit spans, ~0.8 GB)
         nf = nfiles // 4
         k = int((offs < nf * (flat.numel() // nfiles)).sum().item())
@@ -911,8 +965,10 @@ def run_config5(args, world, rank, dev, stream):
     for rep in reports:
         assert rep.ok and rep.n_stale == args.finalised, (rep.ok, rep.n_bad, rep.n_stale, rep.walk_errors[:5])
     rep = reports[-1]
+    dump_outputs(args, world, rank, {"report": np.array([rep.ok, rep.files, rep.commits, rep.bytes_checked,
+                                                          rep.n_bad, rep.n_stale])})
     # the checker over the whole DB (rank 0; every rank holds the same images)
-    parity = oracle_check_db(job.db, args.finalised) if rank == 0 else None
+    parity = oracle_check_db(job.db, args.finalised) if args.full and rank == 0 else None
     if parity and parity["mismatches"]:
         raise SystemExit(f"config5: the oracle disagrees: {parity}")
     kern_ms = float(np.mean(tm.kern_ms))
@@ -928,7 +984,7 @@ def run_config5(args, world, rank, dev, stream):
                                  f".zsdb), {rep.commits} commits", "db_bytes": job.plan.weight,
                      "files": rep.files, "commits": rep.commits,
                      "parallelism": f"split{world}" + ("+allgather_digests" if world > 1 else "")},
-                    r, scaling="strong", parity=parity,
+                    r, scaling="strong", **({"parity": parity} if args.full else {}),
                     data="synthetic zeroskip DB generated on the GPU (tools/zsdb_gen.py), device-resident",
                     prepare={k: round(v, 4) if isinstance(v, float) else v for k, v in job.prepare_times.items()},
                     device_pass={"verified_spans": len(job.c_off), "longest_verified_span": job.c_max,
@@ -938,7 +994,7 @@ def run_config5(args, world, rank, dev, stream):
                             "note": "every pass's report collected and checked inside the timed region; "
                                     "pipelined: pass k's copy back read while pass k + 1 runs"},
                     gen_s=round(t_gen, 2), open_s=round(t_open, 2))
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # 64 finalised files' commit spans + 768 MiB of a packed records region
         fin = [f for f in job.db.files if f.kind == zsfile.FINALISED][:64]
         so = [zsfile.walk(f.image)[:2] for f in fin]
@@ -978,12 +1034,19 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="config3", choices=["config2", "config3", "config4", "config5"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-e2e", action="store_true", help="config4: skip the end-to-end leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured or checked beside the headline: CPU baseline, oracle parity, "
+                         "sustained rate, each workload's side legs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-e2e", action="store_true", help="--full, config4: skip the end-to-end leg")
     ap.add_argument("--pairs", type=int, default=10_000_000, help="config4 pairs per GPU")
     ap.add_argument("--packed-mib", type=int, default=3072, help="config5 packed records region size")
     ap.add_argument("--finalised", type=int, default=1024, help="config5 finalised files")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # --gpus N without a launcher: one process per GPU is the contract, so

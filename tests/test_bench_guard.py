@@ -31,6 +31,32 @@ def test_world_size_mismatch_is_an_error():
     assert p.returncode != 0 and "WORLD_SIZE=2" in (p.stderr + p.stdout)
 
 
+def test_dump_outputs_writes_float64_within_the_limit(tmp_path):
+    """--dump-outputs DIR: one DIR/<name>.npy per array, float64 (exact for
+    32-bit CRCs), per-rank names with more than one rank, at most 64 MB."""
+    import argparse
+    import numpy as np
+    import pytest
+    import bench
+    crc = np.array([0, 1, 0x80000000, 0xFFFFFFFF], dtype=np.uint32)
+    args = argparse.Namespace(dump_outputs=str(tmp_path / "d"))
+    bench.dump_outputs(args, 1, 0, {"crc": crc})
+    got = np.load(tmp_path / "d" / "crc.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.uint32), crc)
+    bench.dump_outputs(args, 2, 1, {"crc": crc})
+    assert (tmp_path / "d" / "crc_rank1.npy").exists()
+    assert bench.DUMP_MAX_BYTES == 64 << 20
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(args, 1, 0, {"big": np.zeros((64 << 20) // 8 + 1, dtype=np.uint32)})
+
+
+def test_full_and_dump_outputs_are_options():
+    p = _run(["--help"])
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+    p = _run(["--steps", "0"])
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
 def test_traffic_only_for_its_own_kernel():
     """a PMC traffic record is reported only on the line of the
     kernel it was measured on (profiles/pmc_traffic.json is keyed by config

@@ -4,6 +4,8 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+O=${O:-bench_lines}   # where the bench lines go
+mkdir -p $O
 T="python -u -m pytest --maxfail=10 -q --timeout 300 --timeout-method thread"
 for step in "$@"; do
   case "$step" in
@@ -15,16 +17,16 @@ for step in "$@"; do
     gputests) timeout -k 10 900 $T -m gpu tests > gpurun_out/gputests.log 2>&1 ;;
     smoke)    timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 ;;
     bench2|bench3|bench4|bench5)
-              timeout -k 10 600 python bench.py --workload config${step#bench} > gpurun_out/$step.json \
-                2> gpurun_out/$step.err ;;
-    bench4s)  ZSCRC_OPT=4194304 timeout -k 10 600 python bench.py --workload config4 --no-e2e --no-cpu \
-                >> gpurun_out/bench4s.jsonl 2>> gpurun_out/bench4s.err ;;
-    bench4q)  timeout -k 10 600 python bench.py --workload config4 --no-e2e --no-cpu \
-                >> gpurun_out/bench4q.jsonl 2>> gpurun_out/bench4q.err ;;
+              timeout -k 10 600 python bench.py --full --workload config${step#bench} > $O/$step.json \
+                2> $O/$step.err ;;
+    bench4s)  ZSCRC_OPT=4194304 timeout -k 10 600 python bench.py --full --workload config4 --no-e2e --no-cpu \
+                >> $O/bench4s.jsonl 2>> $O/bench4s.err ;;
+    bench4q)  timeout -k 10 600 python bench.py --full --workload config4 --no-e2e --no-cpu \
+                >> $O/bench4q.jsonl 2>> $O/bench4q.err ;;
     bench5q|bench5s|bench5x)   # config 5: default / static commit rounds (1 << 22) / static span segments (1 << 26)
               case "$step" in bench5q) o=0 ;; bench5s) o=4194304 ;; bench5x) o=67108864 ;; esac
-              ZSCRC_OPT=$o timeout -k 10 600 python bench.py --workload config5 --no-cpu \
-                >> gpurun_out/$step.jsonl 2>> gpurun_out/$step.err ;;
+              ZSCRC_OPT=$o timeout -k 10 600 python bench.py --full --workload config5 --no-cpu \
+                >> $O/$step.jsonl 2>> $O/$step.err ;;
     abspan)   AB_CASES=span_3GiB,spans_config5 timeout -k 10 600 python tools/opt_ab.py 0 67108864 \
                 > gpurun_out/abspan.jsonl 2> gpurun_out/abspan.err ;;
     pmc4box)  timeout -k 10 180 python -c "import json, bench; print(json.dumps(bench.box_info(0)))" > gpurun_out/box4.json \
@@ -54,15 +56,15 @@ for step in "$@"; do
                 > gpurun_out/spantests.log 2>&1 ;;
     fillsweep) timeout -k 10 600 python tools/probes/fill_sweep.py > gpurun_out/fill_sweep.jsonl 2> gpurun_out/fill_sweep.err ;;
     rehearse3)
-              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 600 python bench.py --gpus 2 --workload config3 \
-                --no-cpu > gpurun_out/rehearse3_n2.json 2> gpurun_out/rehearse3_n2.err ;;
+              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 600 python bench.py --full --gpus 2 --workload config3 \
+                --no-cpu > $O/rehearse3_n2.json 2> $O/rehearse3_n2.err ;;
     rehearse5)
-              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 900 python bench.py --gpus 2 --workload config5 \
-                --no-cpu > gpurun_out/rehearse5_n2.json 2> gpurun_out/rehearse5_n2.err ;;
+              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 900 python bench.py --full --gpus 2 --workload config5 \
+                --no-cpu > $O/rehearse5_n2.json 2> $O/rehearse5_n2.err ;;
     rehearse5x8)
-              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 900 python bench.py --gpus 8 --workload config5 \
-                --no-cpu --packed-mib 1024 --finalised 256 > gpurun_out/rehearse5_n8.json \
-                2> gpurun_out/rehearse5_n8.err ;;
+              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 900 python bench.py --full --gpus 8 --workload config5 \
+                --no-cpu --packed-mib 1024 --finalised 256 > $O/rehearse5_n8.json \
+                2> $O/rehearse5_n8.err ;;
     cwaves)   timeout -k 10 600 python tools/probes/commit_waves.py > gpurun_out/commit_waves.jsonl 2> gpurun_out/commit_waves.err ;;
     ab4split) AB_CASES=config4_verdict,config4_crcs,config4_write,config4_verify timeout -k 10 600 python tools/opt_ab.py \
                 0 536870912 > gpurun_out/ab4split.jsonl 2> gpurun_out/ab4split.err ;;
@@ -72,29 +74,29 @@ for step in "$@"; do
                 0 16384 2147483648 536870912 > gpurun_out/ab4final.jsonl 2> gpurun_out/ab4final.err ;;
     ab4tail)  AB_CASES=config4_verdict,config4_crcs,config4_write,config4_verify timeout -k 10 600 python tools/opt_ab.py \
                 0 2147483648 2147484160 > gpurun_out/ab4tail.jsonl 2> gpurun_out/ab4tail.err ;;
-    bench4t)  ZSCRC_OPT=2147483648 timeout -k 10 600 python bench.py --workload config4 --no-e2e --no-cpu \
-                >> gpurun_out/bench4t.jsonl 2> gpurun_out/bench4t.err ;;
-    bench4u)  ZSCRC_OPT=2147484160 timeout -k 10 600 python bench.py --workload config4 --no-e2e --no-cpu \
-                >> gpurun_out/bench4u.jsonl 2> gpurun_out/bench4u.err ;;
-    bench4d)  timeout -k 10 600 python bench.py --workload config4 --no-e2e --no-cpu \
-                >> gpurun_out/bench4d.jsonl 2> gpurun_out/bench4d.err ;;
-    bench4l)  ZSCRC_OPT=16384 timeout -k 10 600 python bench.py --workload config4 --no-e2e --no-cpu \
-                >> gpurun_out/bench4l.jsonl 2> gpurun_out/bench4l.err ;;
-    benchdef) timeout -k 10 600 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err ;;
+    bench4t)  ZSCRC_OPT=2147483648 timeout -k 10 600 python bench.py --full --workload config4 --no-e2e --no-cpu \
+                >> $O/bench4t.jsonl 2> $O/bench4t.err ;;
+    bench4u)  ZSCRC_OPT=2147484160 timeout -k 10 600 python bench.py --full --workload config4 --no-e2e --no-cpu \
+                >> $O/bench4u.jsonl 2> $O/bench4u.err ;;
+    bench4d)  timeout -k 10 600 python bench.py --full --workload config4 --no-e2e --no-cpu \
+                >> $O/bench4d.jsonl 2> $O/bench4d.err ;;
+    bench4l)  ZSCRC_OPT=16384 timeout -k 10 600 python bench.py --full --workload config4 --no-e2e --no-cpu \
+                >> $O/bench4l.jsonl 2> $O/bench4l.err ;;
+    benchdef) timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ;;
     ab2nt)    AB_CASES=config2_multi32,config2_warm32 timeout -k 10 600 python tools/opt_ab.py 0 64 > gpurun_out/ab2nt.jsonl \
                 2> gpurun_out/ab2nt.err ;;
-    bench2nt) ZSCRC_OPT=64 timeout -k 10 600 python bench.py --workload config2 --no-cpu >> gpurun_out/bench2nt.jsonl \
-                2> gpurun_out/bench2nt.err ;;
-    bench2d)  timeout -k 10 600 python bench.py --workload config2 --no-cpu >> gpurun_out/bench2d.jsonl \
-                2> gpurun_out/bench2d.err ;;
+    bench2nt) ZSCRC_OPT=64 timeout -k 10 600 python bench.py --full --workload config2 --no-cpu >> $O/bench2nt.jsonl \
+                2> $O/bench2nt.err ;;
+    bench2d)  timeout -k 10 600 python bench.py --full --workload config2 --no-cpu >> $O/bench2d.jsonl \
+                2> $O/bench2d.err ;;
     sustain45) PC_TIME=1 timeout -k 10 300 python tools/prof_case.py config4 200 > gpurun_out/sustain_config4.json \
                 2> gpurun_out/sustain.err && PC_TIME=1 timeout -k 10 300 python tools/prof_case.py config5 200 \
                 > gpurun_out/sustain_config5.json 2>> gpurun_out/sustain.err ;;
-    bench3d)  timeout -k 10 600 python bench.py --workload config3 --no-cpu >> gpurun_out/bench3d.jsonl 2> gpurun_out/bench3d.err ;;
-    bench3f)  ZSCRC_OPT=32 timeout -k 10 600 python bench.py --workload config3 --no-cpu >> gpurun_out/bench3f.jsonl \
-                2> gpurun_out/bench3f.err ;;
-    bench4h)  ZSCRC_LIB_PATH=$PWD/zeroskip_amd/libzscrc_head.so timeout -k 10 600 python bench.py --workload config4 \
-                --no-e2e --no-cpu >> gpurun_out/bench4h.jsonl 2> gpurun_out/bench4h.err ;;
+    bench3d)  timeout -k 10 600 python bench.py --full --workload config3 --no-cpu >> $O/bench3d.jsonl 2> $O/bench3d.err ;;
+    bench3f)  ZSCRC_OPT=32 timeout -k 10 600 python bench.py --full --workload config3 --no-cpu >> $O/bench3f.jsonl \
+                2> $O/bench3f.err ;;
+    bench4h)  ZSCRC_LIB_PATH=$PWD/zeroskip_amd/libzscrc_head.so timeout -k 10 600 python bench.py --full --workload config4 \
+                --no-e2e --no-cpu >> $O/bench4h.jsonl 2> $O/bench4h.err ;;
     ab4steal) AB_CASES=config4_verdict,config4_crcs,config4_write,config4_verify timeout -k 10 600 python tools/opt_ab.py \
                 0 512 16384 > gpurun_out/ab4steal.jsonl 2> gpurun_out/ab4steal.err ;;
     cwavesb)  timeout -k 10 600 python tools/probes/commit_waves.py base > gpurun_out/commit_waves_base.jsonl 2> gpurun_out/commit_waves.err ;;

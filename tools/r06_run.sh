@@ -21,10 +21,10 @@ for step in "$@"; do
     soaklong) ZSCRC_SOAK_SEEDS=250 ZSCRC_SOAK_COMMITS=240 ZSCRC_SOAK_CONSISTENT=60 timeout -k 10 900 \
                 $T tests/test_gpu_soak.py tests/test_gpu_consistent.py -k "random" > $O/soaklong.log 2>&1 ;;
     bench2|bench3|bench4|bench5)
-              timeout -k 10 900 python bench.py --workload config${step#bench} >> $O/$step.jsonl 2>> $O/$step.err ;;
+              timeout -k 10 900 python bench.py --full --workload config${step#bench} >> $O/$step.jsonl 2>> $O/$step.err ;;
     bench2q|bench3q|bench4q|bench5q)   # GPU part only
               c=${step#bench}; c=${c%q}
-              timeout -k 10 600 python bench.py --workload config$c --no-cpu --no-e2e >> $O/$step.jsonl \
+              timeout -k 10 600 python bench.py --full --workload config$c --no-cpu --no-e2e >> $O/$step.jsonl \
                 2>> $O/$step.err ;;
     trace2|trace3|trace4|trace5)
               c=config${step#trace}
@@ -35,10 +35,10 @@ for step in "$@"; do
               c=config${step#traffic}
               bash tools/pmc_traffic.sh $c 5 ;;
     rehearse3)
-              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 600 python bench.py --gpus 2 --workload config3 \
+              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 600 python bench.py --full --gpus 2 --workload config3 \
                 --no-cpu > $O/rehearse3_n2.json 2> $O/rehearse3_n2.err ;;
     rehearse5)
-              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 900 python bench.py --gpus 2 --workload config5 \
+              BENCH_SHARE_GPU=1 BENCH_DIST=gloo timeout -k 10 900 python bench.py --full --gpus 2 --workload config5 \
                 --no-cpu > $O/rehearse5_n2.json 2> $O/rehearse5_n2.err ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
