@@ -412,6 +412,68 @@ typedef struct zscrc_zs_report {
  * current device, verify every commit there.  Synchronous. */
 int zscrc_zs_verify_image(const void *image, uint64_t size, int kind, zscrc_zs_report *rep);
 
+/* The walk on the device: zscrc_zs_walk for an image that lives in device
+ * memory (written there by zscrc_device_write_commits, received from another
+ * rank, kept resident between passes) -- the image never crosses PCIe.  Three
+ * launches on `stream` (a table of where a walk entering each block at each
+ * 8-byte slot leaves it, a chain of one hop per block, the emit of the spans
+ * at prefix-summed positions), no workgroup waiting for another one.
+ * Options: the chain's granularity and the LDS tile, both powers of two,
+ * 64 <= tile_bytes <= block_bytes <= 1 GiB and tile_bytes <= 16 KiB; 0 = the
+ * default (1 MiB, 16 KiB; the default tile is cut to a smaller block).  An
+ * image may have at most 2^24 - 1 blocks (one workgroup each): 16 TiB at the
+ * default, 1 GiB at block_bytes 64; more is a bad option. */
+typedef struct zscrc_walk_opts {   /* NULL = defaults */
+    uint64_t block_bytes;          /* chain granularity; 0 = default; a power of two >= 64 */
+    uint64_t tile_bytes;           /* LDS tile; 0 = default; a power of two, 64 <= tile <= block */
+} zscrc_walk_opts;
+#define ZSCRC_WALK_SERIAL 1u       /* the one-lane walk only (diagnostic / cross-check) */
+#define ZSCRC_WALK_RES_WORDS 6
+/* Bytes of scratch zscrc_device_walk needs for an image of image_size bytes:
+ * 8 per 8-byte slot of the image and 16 per block, so at most
+ * image_size + 24 * blocks; monotone in image_size.  0 = bad options (also:
+ * more than 2^24 - 1 blocks). */
+size_t zscrc_device_walk_scratch_bytes(uint64_t image_size, const zscrc_walk_opts *opts);
+/* Asynchronous on `stream`.  d_span_off / d_span_len (device, cap entries)
+ * receive the spans in ascending offset order, exactly zscrc_zs_walk's for the
+ * same bytes; entries at index >= cap are not written (cap 0: the pointers
+ * may be NULL).  d_res (device, ZSCRC_WALK_RES_WORDS words):
+ *   [0] zscrc_zs_walk's result code for the same bytes and cap
+ *       (ZSCRC_ZS_OVERFLOW when there are more commits than cap)
+ *   [1] the number of commits, all of them counted even past cap
+ *   [2] end_off
+ *   [3] the longest span length, [4] the shortest, over all commits (0 when
+ *       there is none): what zscrc_device_verify_commits_verdict_range and
+ *       the _bounded entry points want
+ *   [5] the offset at which a one-lane serial walk took over from the chain
+ *       (a corrupt value offset led the walk to an offset that is no multiple
+ *       of 8), UINT64_MAX if none did -- also when the whole walk was the
+ *       one-lane one (ZSCRC_WALK_SERIAL, or an image of less than one tile)
+ * scratch: 16-byte aligned device memory of zscrc_device_walk_scratch_bytes
+ * bytes, or NULL for library-owned scratch (stream-ordered between calls like
+ * zscrc_device_span's; one buffer per device of exactly the largest size a
+ * call there needed, i.e. about the size of the largest image walked, kept
+ * until zscrc_release_cache).  The one-lane walk (ZSCRC_WALK_SERIAL, images
+ * of less than one tile) uses no scratch at all.  ZSCRC_EINVAL for
+ * image_size < 40 or bad options, as the host walk. */
+int zscrc_device_walk(const void *d_image, uint64_t image_size,
+                      uint64_t *d_span_off, uint64_t *d_span_len, size_t cap,
+                      uint64_t *d_res, void *scratch, const zscrc_walk_opts *opts,
+                      unsigned flags, void *stream);
+/* zscrc_zs_verify_image for a device-resident image, the same report field
+ * for field: the 40-byte header (packed files: also the few words that locate
+ * the two spans) is copied to the host, the walk and every commit CRC run on
+ * the device.  Synchronous.  Device memory on top of the image, ACTIVE /
+ * FINALISED: the walk's library scratch (about the image's size, kept, see
+ * zscrc_device_walk) and, for the call's duration, 24 bytes per commit slot --
+ * room for one commit per 64 bytes of image first (37.5 % of the image's
+ * size), and only if the image holds more a second walk with room for the
+ * count the first one found.  PACKED: 96 bytes.  A caller short of memory
+ * walks with its own cap and scratch (zscrc_device_walk, cap 0 counts only)
+ * and verifies with zscrc_device_verify_commits_verdict. */
+int zscrc_device_verify_image(const void *d_image, uint64_t image_size, int kind,
+                              zscrc_zs_report *rep, void *stream);
+
 /* `consistent` for one process / one GPU (zsdb_consistent,
  * src/zeroskip.c:1399-1407, and tool/cmd-consistent.c:23-49 are stubs in the
  * reference): every .zsdb / header / commit CRC of the DB directory,

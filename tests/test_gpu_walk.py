@@ -1,0 +1,436 @@
+"""The device walk (zscrc_device_walk, zeroskip_amd/csrc/zscrc_walk.hip) and
+zscrc_device_verify_image against the host walk / zscrc_zs_verify_image on
+the same bytes: spans, count, result code and end offset equal, at the default
+geometry and at blocks / tiles small enough that every boundary case occurs
+inside a few KiB."""
+import random
+import struct
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import zs_format as zf
+from tests import fuzzlib
+from tests.test_format_oracle import UUID, build_active
+from zeroskip_amd import zsfile
+
+pytestmark = pytest.mark.gpu
+
+# (block_bytes, tile_bytes); 0 = the library's default
+OPTSETS = [(0, 0), (64, 64), (512, 64), (4096, 512)]
+OPT_IDS = ["default", "b64_t64", "b512_t64", "b4096_t512"]
+SMALL = OPTSETS[1:]
+U64_MAX = (1 << 64) - 1
+PAD = 4096
+CANARY = 0xA5
+T_2ND = zf.REC_2ND_HALF
+
+
+def _dev(img: bytes, dev) -> torch.Tensor:
+    return torch.from_numpy(np.frombuffer(img, dtype=np.uint8).copy()).to(dev)
+
+
+def _host(img: bytes):
+    off, ln, rc, end = zsfile.walk(img)
+    return off.astype(np.uint64), ln.astype(np.uint64), rc, end
+
+
+def _u64(t: torch.Tensor) -> np.ndarray:
+    return t.cpu().numpy().view(np.uint64)
+
+
+def _device(d, block=0, tile=0, serial=False):
+    off, ln, res = zsfile.device_walk(d, block_bytes=block, tile_bytes=tile, serial=serial)
+    r = _u64(res)
+    n = int(r[1])
+    return _u64(off[:n]), _u64(ln[:n]), r
+
+
+def _same(img: bytes, d, block, tile, serial=False):
+    """The device walk of d equals the host walk of img; returns its res."""
+    hoff, hlen, hrc, hend = _host(img)
+    off, ln, r = _device(d, block, tile, serial)
+    what = (len(img), block, tile, serial)
+    assert (int(r[0]), int(r[1]), int(r[2])) == (hrc, len(hoff), hend), what
+    assert np.array_equal(off, hoff) and np.array_equal(ln, hlen), what
+    assert int(r[3]) == (int(hlen.max()) if len(hlen) else 0), what
+    assert int(r[4]) == (int(hlen.min()) if len(hlen) else 0), what
+    return r
+
+
+# ------------------------------------------------------------ crafted images
+def short_commit(span_len=0, final=False):
+    return zf.be64(((zf.REC_FINAL if final else zf.REC_COMMIT) << 56) | (span_len << 32))
+
+
+def long_commit(span_len):
+    return zf.be64(zf.REC_LONG_COMMIT << 56) + zf.be64(span_len) + zf.be64(T_2ND << 56)
+
+
+def long_key(key: bytes):
+    kbuflen = 24 + zf.rup8(len(key))
+    return zf.be64(zf.REC_LONG_KEY << 56) + zf.be64(len(key)) + zf.be64(kbuflen) + key + \
+        bytes(kbuflen - 24 - len(key))
+
+
+class Img:
+    """Records laid one after another from the header; pad_to() fills with
+    delete records (and 8-byte commits) up to a wanted offset."""
+
+    def __init__(self):
+        self.b = bytearray(zf.header_bytes(UUID, 1, 1))
+
+    def __len__(self):
+        return len(self.b)
+
+    def add(self, rec: bytes) -> int:
+        at = len(self.b)
+        self.b += rec
+        return at
+
+    def pad_to(self, off: int):
+        assert off >= len(self.b) and off % 8 == 0
+        while len(self.b) < off:
+            gap = off - len(self.b)
+            if gap in (8, 16, 32):
+                self.b += short_commit(0)
+            else:
+                self.b += zf.delete_record(bytes([0x41]) * min(gap - 24, 4096))
+
+    def next_at(self, mod: int, rem: int, least: int = 0) -> int:
+        """Pad to the next offset == rem (mod `mod`) that leaves `least` bytes
+        of ordinary records before it; returns it."""
+        self.add(zf.key_record(b"k" * 9) + zf.value_record(b"v" * 21))
+        off = len(self.b) + least
+        off += (rem - off) % mod
+        self.pad_to(off)
+        return off
+
+    def image(self) -> bytes:
+        return bytes(self.b)
+
+
+def boundary_cases(B: int, T: int):
+    """[(name, image)] against tile T and block B; each case is checked here
+    to be what its name says, before any GPU work."""
+    out = []
+
+    im = Img()
+    a = im.next_at(T, T - 8)
+    im.add(short_commit(a - 40))
+    b = im.next_at(T, 0)
+    im.add(short_commit(8))
+    assert a % T == T - 8 and b % T == 0
+    out.append(("short_commit_last_and_first_slot", im.image()))
+
+    im = Img()
+    a = im.next_at(T, T - 8)
+    im.add(long_commit(a - 40))
+    b = im.next_at(B, B - 16)
+    im.add(long_commit(100))
+    im.add(zf.key_record(b"after") + zf.value_record(b"x" * 50) + short_commit(8))
+    assert a // T != (a + 23) // T and b // B != (b + 23) // B
+    out.append(("long_commit_straddles_tile_and_block", im.image()))
+
+    im = Img()
+    a = im.next_at(B, B - 8)
+    im.add(zf.key_record(b"K" * 40) + zf.value_record(b"V" * 70) + short_commit(16))
+    voff = struct.unpack(">Q", im.b[a:a + 8])[0] & 0xFFFFFFFF
+    assert a % B == B - 8 and (a + voff) // B == a // B + 1
+    out.append(("key_header_last_slot_of_block", im.image()))
+
+    im = Img()
+    a = im.next_at(B, B - 8)
+    im.add(long_key(b"L" * 33) + zf.value_record(b"W" * 9) + short_commit(0))
+    b = im.next_at(T, T - 16)
+    im.add(long_key(b"M" * 8) + zf.value_record(b"") + short_commit(24))
+    assert (a + 16) // B == a // B + 1 and (b + 16) // T == b // T + 1
+    out.append(("long_key_header_straddles", im.image()))
+
+    im = Img()
+    im.add(zf.key_record(b"big") + zf.value_record(bytes(range(256)) * ((2 * B + 300) // 256 + 1)))
+    a = im.add(short_commit(64))
+    im.add(zf.key_record(b"tail") + zf.value_record(b"t") + short_commit(8))
+    assert 40 // B == 0 and a // B >= 2  # the walk enters no block in between
+    out.append(("value_longer_than_two_blocks", im.image()))
+
+    im = Img()
+    im.next_at(B, B - 8)
+    im.add(short_commit(32))
+    assert len(im) % B == 0
+    out.append(("ends_on_block_boundary", im.image()))
+
+    im = Img()
+    im.next_at(T, 8)
+    a = im.add(short_commit(16, final=True))
+    im.add(zf.key_record(b"never") + zf.value_record(b"seen") + short_commit(8))
+    out.append(("final_mid_file", im.image()))
+    assert _host(im.image())[2:] == (zsfile.STOPPED, a)
+
+    hdr = zf.header_bytes(UUID, 1, 1)
+    out.append(("size_40", hdr))
+    h = _host(hdr)
+    assert (len(h[0]), h[2], h[3]) == (0, zsfile.END, 40)
+    for extra in range(1, 8):
+        img = hdr + bytes([4]) * extra
+        h = _host(img)
+        assert (len(h[0]), h[2], h[3]) == (0, zsfile.TRUNCATED, 40)
+        out.append((f"size_{40 + extra}", img))
+    return out
+
+
+def unaligned_image(prefix: bytes):
+    """prefix + a key record whose value offset points 28 bytes on, into the
+    key's own bytes, at a short value header placed there (offset = 4 mod 8);
+    the walk goes on at key + 52, where a commit word stands, and ends at
+    key + 60 = the image's end.  Returns (image, first unaligned offset)."""
+    assert len(prefix) % 8 == 0
+    K = len(prefix)
+    key = bytearray(64)
+    key[4:12] = zf.be64((zf.REC_VALUE << 56) | (8 << 32))
+    key[28:36] = short_commit(12)
+    rec = bytearray(zf.key_record(bytes(key)))
+    rec[0:8] = zf.be64((zf.REC_KEY << 56) | (64 << 40) | 28)
+    img = prefix + bytes(rec[:60])
+    assert (K + 28) % 8 == 4 and (K + 52) % 8 == 4
+    return img, K + 52
+
+
+@pytest.fixture(scope="module")
+def wellformed():
+    return build_active(200, seed=11)
+
+
+# --------------------------------------------------------------------- tests
+@pytest.mark.parametrize("block,tile", OPTSETS, ids=OPT_IDS)
+def test_wellformed(gpu, wellformed, block, tile):
+    img = wellformed
+    assert len(img) > 16384  # more than one default tile: the three-launch path at the default too
+    r = _same(img, _dev(img, gpu), block, tile)
+    assert int(r[0]) == zsfile.END and int(r[1]) == 200
+    assert int(r[5]) == U64_MAX
+
+
+@pytest.fixture(scope="module")
+def fuzz_images():
+    """600 mutated images and the host walk of each."""
+    w = zf.FileWriter(UUID, idx=2)
+    for t in range(6):
+        for i in range(40):
+            w.add(b"%08d" % (t * 100 + i), bytes([i]) * (i * 7 % 200))
+        w.commit()
+    long_tx = w.image()
+    w = zf.FileWriter(UUID, idx=4)
+    w.add(b"a", b"b")
+    w.commit()
+    w.add(bytes(range(256)) * 273 + b"tail" * 28, b"value of the long key")
+    w.commit()
+    w.add(b"z", b"")
+    w.commit()
+    key70k = w.image()
+    assert len(key70k) > 70000
+    w = zf.FileWriter(UUID, idx=5)
+    for t in range(12):
+        w.add(b"f%04d" % t, b"q" * (t * 13))
+        w.commit()
+    w.finalise()
+    bases = [build_active(30, seed=2), long_tx, key70k, w.image()]
+    rng = random.Random(7)
+    imgs = []
+    while len(imgs) < 600:
+        m = fuzzlib.mutate(rng, rng.choice(bases))
+        if len(m) > 40:
+            imgs.append(m)
+    return [(m, _host(m)) for m in imgs]
+
+
+def test_fuzz(fuzz_images, gpu):
+    # the three outcomes each make up a fair share, from the host walk alone
+    for rc in (zsfile.END, zsfile.STOPPED, zsfile.TRUNCATED):
+        share = sum(1 for _, h in fuzz_images if h[2] == rc) / len(fuzz_images)
+        print(f"host walk result {rc}: {share:.3f} of {len(fuzz_images)} images")
+        assert share >= 0.10, (rc, share)
+    for img, (hoff, hlen, hrc, hend) in fuzz_images:
+        d = _dev(img, gpu)
+        for block, tile in OPTSETS:
+            off, ln, r = _device(d, block, tile)
+            assert (int(r[0]), int(r[1]), int(r[2])) == (hrc, len(hoff), hend), (len(img), block, tile)
+            assert np.array_equal(off, hoff) and np.array_equal(ln, hlen), (len(img), block, tile)
+
+
+@pytest.mark.parametrize("B,T", SMALL, ids=OPT_IDS[1:])
+def test_boundaries(gpu, B, T):
+    for name, img in boundary_cases(B, T):
+        d = _dev(img, gpu)
+        for block, tile in OPTSETS:
+            r = _same(img, d, block, tile)
+            assert int(r[5]) == U64_MAX, name
+            _same(img, d, block, tile, serial=True)
+
+
+@pytest.mark.parametrize("block,tile", OPTSETS, ids=OPT_IDS)
+def test_unaligned_continuation(gpu, wellformed, block, tile):
+    img, first = unaligned_image(wellformed)
+    hoff, hlen, hrc, hend = _host(img)
+    assert (hrc, hend, len(hoff)) == (zsfile.END, len(img), 201) and hend % 8 == 4
+    d = _dev(img, gpu)
+    r = _same(img, d, block, tile)
+    assert int(r[5]) == first
+    r = _same(img, d, block, tile, serial=True)
+    assert int(r[5]) == U64_MAX  # the whole walk was the one-lane one
+
+
+def _fenced(nbytes: int, dev):
+    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
+    return whole, whole[PAD:PAD + nbytes]
+
+
+def _intact(whole: torch.Tensor, nbytes: int) -> bool:
+    h = whole.cpu().numpy()
+    return bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all())
+
+
+@pytest.mark.parametrize("block,tile", OPTSETS, ids=OPT_IDS)
+def test_cap(gpu, wellformed, block, tile):
+    img = wellformed
+    hoff, hlen, hrc, hend = _host(img)
+    n = len(hoff)
+    d = _dev(img, gpu)
+    for cap in (n // 2, 0):
+        # cap 0 too gets real arrays (one entry's room): nothing may be stored there
+        room = max(cap, 1) * 8
+        fo, off = _fenced(room, gpu)
+        fl, ln = _fenced(room, gpu)
+        fr, res = _fenced(8 * zsfile.WALK_RES_WORDS, gpu)
+        assert off.data_ptr() and ln.data_ptr()
+        zsfile.device_walk(d, cap=cap, block_bytes=block, tile_bytes=tile,
+                           out=(off.view(torch.int64), ln.view(torch.int64), res.view(torch.int64)))
+        r = _u64(res.view(torch.int64))
+        assert int(r[0]) == zsfile.OVERFLOW and int(r[1]) == n and int(r[2]) == hend
+        assert int(r[3]) == int(hlen.max()) and int(r[4]) == int(hlen.min())
+        assert np.array_equal(_u64(off.view(torch.int64))[:cap], hoff[:cap])
+        assert np.array_equal(_u64(ln.view(torch.int64))[:cap], hlen[:cap])
+        if cap == 0:  # the entry the arrays have room for is untouched
+            assert bool((off == CANARY).all()) and bool((ln == CANARY).all())
+        assert _intact(fo, room) and _intact(fl, room) and _intact(fr, 8 * zsfile.WALK_RES_WORDS)
+    # cap 0 with no arrays at all (the pointers may be NULL then)
+    _, _, res = zsfile.device_walk(d, cap=0, block_bytes=block, tile_bytes=tile,
+                                   out=(torch.empty(0, dtype=torch.int64, device=gpu),
+                                        torch.empty(0, dtype=torch.int64, device=gpu),
+                                        torch.empty(zsfile.WALK_RES_WORDS, dtype=torch.int64, device=gpu)))
+    r = _u64(res)
+    assert int(r[0]) == zsfile.OVERFLOW and int(r[1]) == n and int(r[2]) == hend
+
+
+def test_serial_flag_on_wellformed(gpu, wellformed):
+    _same(wellformed, _dev(wellformed, gpu), 0, 0, serial=True)
+
+
+@pytest.mark.parametrize("block,tile", OPTSETS, ids=OPT_IDS)
+def test_caller_scratch_fenced(gpu, wellformed, block, tile):
+    img = wellformed
+    hoff, hlen, hrc, hend = _host(img)
+    need = zsfile.walk_scratch_bytes(len(img), block, tile)
+    assert need > 0
+    whole, scratch = _fenced(need, gpu)
+    assert scratch.data_ptr() % 16 == 0
+    off, ln, res = zsfile.device_walk(_dev(img, gpu), block_bytes=block, tile_bytes=tile, scratch=scratch)
+    r = _u64(res)
+    assert (int(r[0]), int(r[1]), int(r[2])) == (hrc, len(hoff), hend)
+    assert np.array_equal(_u64(off[:len(hoff)]), hoff) and np.array_equal(_u64(ln[:len(hoff)]), hlen)
+    assert _intact(whole, need)
+
+
+def test_scratch_bytes_bound(gpu):
+    # 8 bytes per 8-byte slot and 16 per block: <= image_size + 24 * blocks
+    for block, tile in OPTSETS:
+        bb = block or (1 << 20)
+        last = 0
+        for size in list(range(40, 300)) + [4095, 4096, 4097, (1 << 20) - 1, 1 << 20, (1 << 20) + 1, 5 << 30,
+                                            (32 << 30) + 3]:
+            need = zsfile.walk_scratch_bytes(size, block, tile)
+            blocks = (size + bb - 1) // bb
+            if blocks >= 1 << 24:  # more blocks than one launch has workgroups for: a bad option
+                assert need == 0, (size, block, tile)
+                continue
+            assert last <= need <= size + 24 * blocks, (size, block, tile)
+            last = need
+    assert zsfile.walk_scratch_bytes(1 << 20, 96, 64) == 0     # not a power of two
+    assert zsfile.walk_scratch_bytes(1 << 20, 64, 128) == 0    # tile > block
+    assert zsfile.walk_scratch_bytes(1 << 20, 1 << 20, 32) == 0
+
+
+def _verify_both(img: bytes, kind, dev):
+    want = zsfile.verify_image(img, kind)
+    got = zsfile.verify_device_image(_dev(img, dev), kind)
+    assert got == want, (got, want)
+    return got
+
+
+def test_verify_device_image_active(gpu, wellformed):
+    img = wellformed
+    rep = _verify_both(img, zsfile.ACTIVE, gpu)
+    assert rep["n_commits"] == 200 and rep["n_bad"] == 0 and rep["header_rc"] == 0
+    hoff, hlen, _, _ = _host(img)
+    b = bytearray(img)
+    b[int(hoff[57]) + 3] ^= 0x10                      # a payload byte of commit 57's span
+    rep = _verify_both(bytes(b), zsfile.ACTIVE, gpu)
+    assert rep["n_bad"] == 1 and rep["first_bad"] == 57
+    b = bytearray(img)
+    b[int(hoff[120] + hlen[120]) + 7] ^= 0x01         # commit 120's stored CRC
+    b[int(hoff[33] + hlen[33]) + 6] ^= 0x80
+    rep = _verify_both(bytes(b), zsfile.ACTIVE, gpu)
+    assert rep["n_bad"] == 2 and rep["first_bad"] == 33
+    rep = _verify_both(img[:len(img) * 2 // 3 + 3], zsfile.ACTIVE, gpu)
+    assert rep["walk_rc"] == zsfile.TRUNCATED and 0 < rep["n_commits"] < 200
+    b = bytearray(img)
+    b[9] ^= 1                                         # the header's version field
+    rep = _verify_both(bytes(b), zsfile.FINALISED, gpu)
+    assert rep["header_stored"] != rep["header_computed"]
+
+
+def test_verify_device_image_packed(gpu):
+    recs = sorted((b"%016d" % i, None if i % 11 == 0 else b"y" * (i % 300)) for i in range(5000))
+    img = zf.packed_file(recs, UUID, 2, 9)
+    rep = _verify_both(img, zsfile.PACKED, gpu)
+    assert rep["walk_rc"] == 0 and rep["n_commits"] == 2 and rep["n_bad"] == 0
+    b = bytearray(img)
+    b[-8] = zf.REC_COMMIT                             # the final commit word: no longer FINAL
+    rep = _verify_both(bytes(b), zsfile.PACKED, gpu)
+    assert rep["walk_rc"] == zsfile.TRUNCATED and rep["n_commits"] == 0
+    b = bytearray(img)
+    b[-1] ^= 0x40                                     # its stored CRC
+    rep = _verify_both(bytes(b), zsfile.PACKED, gpu)
+    assert rep["n_bad"] == 1 and rep["first_bad"] == 1
+
+
+def test_verify_device_image_long_commit(gpu):
+    w = zf.FileWriter(UUID)
+    w.add(b"k" * 100, np.random.default_rng(3).integers(0, 256, (17 << 20) + 5, dtype=np.uint8).tobytes())
+    w.commit()
+    w.add(b"small", b"v")
+    w.commit()
+    img = w.image()
+    rep = _verify_both(img, zsfile.ACTIVE, gpu)
+    assert rep["n_commits"] == 2 and rep["n_bad"] == 0
+    # the default geometry's chain skips sixteen blocks here
+    r = _same(img, _dev(img, gpu), 0, 0)
+    assert int(r[3]) > 17 << 20
+
+
+def test_back_to_back_on_a_stream(gpu, wellformed):
+    a = wellformed
+    b = build_active(90, seed=12)
+    da, db = _dev(a, gpu), _dev(b, gpu)
+    torch.cuda.synchronize(gpu)
+    s = torch.cuda.Stream(device=gpu)
+    with torch.cuda.stream(s):
+        ra = zsfile.device_walk(da, block_bytes=4096, tile_bytes=512)
+        rb = zsfile.device_walk(db, block_bytes=512, tile_bytes=64)
+    s.synchronize()
+    for img, (off, ln, res) in ((a, ra), (b, rb)):
+        hoff, hlen, hrc, hend = _host(img)
+        r = _u64(res)
+        assert (int(r[0]), int(r[1]), int(r[2])) == (hrc, len(hoff), hend)
+        assert np.array_equal(_u64(off[:len(hoff)]), hoff) and np.array_equal(_u64(ln[:len(hoff)]), hlen)

@@ -825,6 +825,7 @@ extern "C" int zscrc_files_devices(int *ids, int cap)
 
 extern "C" void zs_fill_release_cache(void);
 extern "C" void zs_scalar_release_cache(void);
+extern "C" void zs_walk_release_cache(void);
 
 extern "C" void zscrc_release_cache(void)
 {
@@ -838,6 +839,7 @@ extern "C" void zscrc_release_cache(void)
         (void)hipSetDevice(cur);
     zs_fill_release_cache();   /* zscrc_zs_fill_commits' pipeline */
     zs_scalar_release_cache(); /* the drop-in symbols' offload stream */
+    zs_walk_release_cache();   /* zscrc_device_walk's scratch */
 }
 
 extern "C" int zscrc_zs_verify_files(const void *const *images, const uint64_t *sizes, const int *kinds, size_t n,

@@ -16,9 +16,11 @@
  *                   the final commit at the end of the file), :278-339
  *   header CRC      src/zeroskip-header.c:105-170 (host-order fields)
  *   .zsdb CRC       src/zeroskip-dotzsdb.c:160-235 (host-order fields)
- * The walk is serial by construction (the next offset depends on the record
- * just parsed), so it runs on the host; every byte of every commit span and
- * every trailer is checksummed and compared on the GPU.
+ * zscrc_zs_walk is the serial form of the walk, for images in host memory;
+ * zscrc_device_walk (zscrc_walk.hip) walks a device-resident
+ * image on the GPU with the same results, and zscrc_device_verify_image below
+ * is zscrc_zs_verify_image for such an image.  Every byte of every commit
+ * span and every trailer is checksummed and compared on the GPU.
  */
 #include <hip/hip_runtime.h>
 
@@ -58,12 +60,33 @@ inline uint32_t be32(const uint8_t *p)
 }
 inline uint64_t rup8(uint64_t n) { return (n + 7) & ~7ull; }
 
+/* Where the record parsers read the image from: host memory, or (the packed
+ * file's few words, zscrc_device_verify_image) device memory one word a copy. */
+struct HostImage {
+    const uint8_t *img;
+    uint64_t word(uint64_t off) const { return be64(img + off); }
+};
+struct DeviceImage {
+    const uint8_t *d_img;
+    hipStream_t stream;
+    mutable bool failed = false;
+    uint64_t word(uint64_t off) const
+    {
+        uint8_t b[8] = {};
+        if (hipMemcpyAsync(b, d_img + off, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            hipStreamSynchronize(stream) != hipSuccess)
+            failed = true;
+        return be64(b);
+    }
+};
+
 /* Length of the commit record at off and its span; false if not a commit. */
-bool commit_at(const uint8_t *img, uint64_t size, uint64_t off, uint64_t *span_len, uint64_t *rec_len)
+template <class Image>
+bool commit_at(const Image &im, uint64_t size, uint64_t off, uint64_t *span_len, uint64_t *rec_len)
 {
     if (off + 8 > size)
         return false;
-    const uint64_t w = be64(img + off);
+    const uint64_t w = im.word(off);
     const unsigned t = (unsigned)(w >> 56);
     if (t == T_COMMIT || t == T_FINAL) {
         *span_len = (w >> 32) & 0xFFFFFF;
@@ -71,12 +94,72 @@ bool commit_at(const uint8_t *img, uint64_t size, uint64_t off, uint64_t *span_l
     } else if (t == T_LONG_COMMIT || t == T_LONG_FINAL) {
         if (off + 24 > size)
             return false;
-        *span_len = be64(img + off + 8);
+        *span_len = im.word(off + 8);
         *rec_len = 24;
     } else {
         return false;
     }
     return *span_len <= off;
+}
+
+/* zscrc_zs_packed_spans for an image in host or device memory. */
+template <class Image>
+int packed_spans(const Image &im, uint64_t size, uint64_t span_off[2], uint64_t span_len[2])
+{
+    if (size < HDR + 16)
+        return ZSCRC_EINVAL;
+    /* final commit at the end: short FINAL, or LONG_FINAL whose 2ND_HALF word
+     * ends the file (get_offset_to_pointers, zeroskip-packed.c:70-131) */
+    uint64_t foff = size - 8;
+    if ((im.word(foff) >> 56) == T_2ND)
+        foff = size - 24;
+    uint64_t sl, rl;
+    if (!commit_at(im, size, foff, &sl, &rl) || rl != size - foff)
+        return ZSCRC_ZS_TRUNCATED;
+    const unsigned ft = (unsigned)(im.word(foff) >> 56);
+    if (ft != T_FINAL && ft != T_LONG_FINAL)
+        return ZSCRC_ZS_TRUNCATED;
+    span_off[1] = foff - sl;
+    span_len[1] = sl;
+    /* the records-region commit ends where the pointer section starts */
+    const uint64_t pstart = foff - sl;
+    if (pstart < HDR + 8)
+        return ZSCRC_ZS_TRUNCATED;
+    uint64_t roff = pstart - 8;
+    if ((im.word(roff) >> 56) == T_2ND && pstart >= HDR + 24)
+        roff = pstart - 24;
+    if (!commit_at(im, size, roff, &sl, &rl) || roff + rl != pstart)
+        return ZSCRC_ZS_TRUNCATED;
+    span_off[0] = roff - sl;
+    span_len[0] = sl;
+    return ZSCRC_OK;
+}
+
+/* The commits' statuses of a device-resident image into the report. */
+int verify_spans(const void *d_image, uint64_t size, const uint64_t *d_off, const uint64_t *d_len, size_t n,
+                 uint64_t max_len, uint32_t *d_crc, uint32_t *d_st, hipStream_t stream, zscrc_zs_report *rep)
+{
+    int rc = zscrc_device_verify_commits_bounded(d_image, size, d_off, d_len, nullptr, n, max_len, d_crc, d_st,
+                                                 stream);
+    if (rc)
+        return rc;
+    uint32_t *st = static_cast<uint32_t *>(malloc(n * 4));
+    if (!st)
+        return ZSCRC_ENOMEM;
+    if (hipMemcpyAsync(st, d_st, n * 4, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) {
+        rc = ZSCRC_EHIP;
+    } else {
+        for (size_t i = 0; i < n; ++i) {
+            if (st[i] != 1) {
+                if (rep->n_bad == 0)
+                    rep->first_bad = i;
+                rep->n_bad++;
+            }
+        }
+    }
+    free(st);
+    return rc;
 }
 
 } /* namespace */
@@ -142,7 +225,7 @@ int zscrc_zs_walk(const void *image, uint64_t size, uint64_t *span_off, uint64_t
             off += 24 + rup8(klen);
         } else if (t == T_COMMIT || t == T_LONG_COMMIT) {
             uint64_t sl, rl;
-            if (!commit_at(img, size, off, &sl, &rl)) {
+            if (!commit_at(HostImage{img}, size, off, &sl, &rl)) {
                 rc = ZSCRC_ZS_TRUNCATED;
                 break;
             }
@@ -166,34 +249,9 @@ int zscrc_zs_walk(const void *image, uint64_t size, uint64_t *span_off, uint64_t
 
 int zscrc_zs_packed_spans(const void *image, uint64_t size, uint64_t span_off[2], uint64_t span_len[2])
 {
-    const uint8_t *img = static_cast<const uint8_t *>(image);
-    if (!img || size < HDR + 16)
+    if (!image)
         return ZSCRC_EINVAL;
-    /* final commit at the end: short FINAL, or LONG_FINAL whose 2ND_HALF word
-     * ends the file (get_offset_to_pointers, zeroskip-packed.c:70-131) */
-    uint64_t foff = size - 8;
-    if ((be64(img + foff) >> 56) == T_2ND)
-        foff = size - 24;
-    uint64_t sl, rl;
-    if (!commit_at(img, size, foff, &sl, &rl) || rl != size - foff)
-        return ZSCRC_ZS_TRUNCATED;
-    const unsigned ft = (unsigned)(be64(img + foff) >> 56);
-    if (ft != T_FINAL && ft != T_LONG_FINAL)
-        return ZSCRC_ZS_TRUNCATED;
-    span_off[1] = foff - sl;
-    span_len[1] = sl;
-    /* the records-region commit ends where the pointer section starts */
-    const uint64_t pstart = foff - sl;
-    if (pstart < HDR + 8)
-        return ZSCRC_ZS_TRUNCATED;
-    uint64_t roff = pstart - 8;
-    if ((be64(img + roff) >> 56) == T_2ND && pstart >= HDR + 24)
-        roff = pstart - 24;
-    if (!commit_at(img, size, roff, &sl, &rl) || roff + rl != pstart)
-        return ZSCRC_ZS_TRUNCATED;
-    span_off[0] = roff - sl;
-    span_len[0] = sl;
-    return ZSCRC_OK;
+    return packed_spans(HostImage{static_cast<const uint8_t *>(image)}, size, span_off, span_len);
 }
 
 int zscrc_zs_header_crc(const void *image, uint64_t size, uint32_t *stored, uint32_t *computed)
@@ -340,21 +398,7 @@ int zscrc_zs_verify_image(const void *image, uint64_t size, int kind, zscrc_zs_r
             uint64_t max_len = 0;
             for (size_t i = 0; i < n; ++i)
                 max_len = len[i] > max_len ? len[i] : max_len;
-            rc = zscrc_device_verify_commits_bounded(dimg, size, doff, dlen, nullptr, n, max_len, dcrc, dst,
-                                                     nullptr);
-            uint32_t *st = static_cast<uint32_t *>(malloc(n * 4));
-            if (!rc && st && hipMemcpy(st, dst, n * 4, hipMemcpyDeviceToHost) == hipSuccess) {
-                for (size_t i = 0; i < n; ++i) {
-                    if (st[i] != 1) {
-                        if (rep->n_bad == 0)
-                            rep->first_bad = i;
-                        rep->n_bad++;
-                    }
-                }
-            } else if (!rc) {
-                rc = ZSCRC_EHIP;
-            }
-            free(st);
+            rc = verify_spans(dimg, size, doff, dlen, n, max_len, dcrc, dst, nullptr, rep);
         }
         if (dimg)
             (void)hipFree(dimg);
@@ -363,6 +407,87 @@ int zscrc_zs_verify_image(const void *image, uint64_t size, int kind, zscrc_zs_r
     }
     free(off);
     free(len);
+    return rc;
+}
+
+int zscrc_device_verify_image(const void *d_image, uint64_t image_size, int kind, zscrc_zs_report *rep, void *stream)
+{
+    if (!d_image || !rep)
+        return ZSCRC_EINVAL;
+    memset(rep, 0, sizeof *rep);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint8_t *dimg = static_cast<const uint8_t *>(d_image);
+    uint8_t hdr[HDR];
+    if (image_size >= HDR &&
+        (hipMemcpyAsync(hdr, dimg, HDR, hipMemcpyDeviceToHost, s) != hipSuccess ||
+         hipStreamSynchronize(s) != hipSuccess))
+        return ZSCRC_EHIP;
+    rep->header_rc = zscrc_zs_header_crc(hdr, image_size >= HDR ? HDR : image_size, &rep->header_stored,
+                                         &rep->header_computed);
+    /* device block of `cap` commits: offsets, lengths, CRCs, statuses (24
+     * bytes a commit), then the walk's result words */
+    void *dmeta = nullptr;
+    size_t n = 0, cap = 2;
+    uint64_t max_len = 0;
+    int rc = ZSCRC_OK;
+    auto block = [&dmeta](size_t c) {
+        return hipMalloc(&dmeta, c * 24 + ZSCRC_WALK_RES_WORDS * 8) == hipSuccess ? ZSCRC_OK : ZSCRC_ENOMEM;
+    };
+    if (kind == ZSCRC_ZS_PACKED) {
+        uint64_t sp[4]; /* two offsets, two lengths */
+        uint64_t so[2], sl[2];
+        const DeviceImage im{dimg, s};
+        rep->walk_rc = packed_spans(im, image_size, so, sl);
+        rep->end_off = image_size;
+        if (im.failed)
+            return ZSCRC_EHIP;
+        if (rep->walk_rc == ZSCRC_OK) {
+            n = 2;
+            sp[0] = so[0], sp[1] = so[1], sp[2] = sl[0], sp[3] = sl[1];
+            max_len = sl[0] > sl[1] ? sl[0] : sl[1];
+            rc = block(cap);
+            if (!rc && (hipMemcpyAsync(dmeta, sp, sizeof sp, hipMemcpyHostToDevice, s) != hipSuccess ||
+                        hipStreamSynchronize(s) != hipSuccess))
+                rc = ZSCRC_EHIP;
+        }
+    } else if (image_size < HDR) {
+        rep->walk_rc = ZSCRC_EINVAL; /* as zscrc_zs_walk */
+    } else {
+        /* most images hold far fewer commits than the bound size / 8 + 1: a
+         * first walk with room for one commit per 64 bytes, and only if that
+         * overflows a second one with room for the count the first one found */
+        uint64_t res[ZSCRC_WALK_RES_WORDS] = {};
+        cap = (size_t)(image_size / 64) + 1;
+        for (int pass = 0; pass < 2; ++pass) {
+            rc = block(cap);
+            if (rc)
+                break;
+            uint64_t *doff = static_cast<uint64_t *>(dmeta), *dres = doff + 3 * cap;
+            rc = zscrc_device_walk(d_image, image_size, doff, doff + cap, cap, dres, nullptr, nullptr, 0, s);
+            if (!rc && (hipMemcpyAsync(res, dres, sizeof res, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                        hipStreamSynchronize(s) != hipSuccess))
+                rc = ZSCRC_EHIP;
+            if (rc || res[1] <= cap)
+                break;
+            (void)hipFree(dmeta);
+            dmeta = nullptr;
+            cap = (size_t)res[1];
+        }
+        if (!rc) {
+            rep->walk_rc = (int)res[0];
+            n = (size_t)res[1];
+            rep->end_off = res[2];
+            max_len = res[3];
+        }
+    }
+    rep->n_commits = n;
+    if (!rc && n) {
+        uint64_t *doff = static_cast<uint64_t *>(dmeta);
+        uint32_t *dcrc = reinterpret_cast<uint32_t *>(doff + 2 * cap);
+        rc = verify_spans(d_image, image_size, doff, doff + cap, n, max_len, dcrc, dcrc + cap, s, rep);
+    }
+    if (dmeta)
+        (void)hipFree(dmeta);
     return rc;
 }
 

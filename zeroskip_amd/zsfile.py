@@ -79,6 +79,64 @@ def verify_image(image, kind: int = ACTIVE) -> dict:
     return rep.as_dict()
 
 
+class WalkOpts(ctypes.Structure):
+    """zscrc_walk_opts (include/zscrc.h)."""
+    _fields_ = [("block_bytes", ctypes.c_uint64), ("tile_bytes", ctypes.c_uint64)]
+
+
+WALK_SERIAL = 1  # ZSCRC_WALK_SERIAL
+WALK_RES_WORDS = 6  # ZSCRC_WALK_RES_WORDS
+WALK_NONE = -1  # res[5] as int64 (UINT64_MAX): no one-lane continuation
+
+
+def walk_scratch_bytes(size: int, block_bytes: int = 0, tile_bytes: int = 0) -> int:
+    """zscrc_device_walk_scratch_bytes; 0 = bad options."""
+    return lib().zscrc_device_walk_scratch_bytes(size, ctypes.byref(WalkOpts(block_bytes, tile_bytes)))
+
+
+def device_walk(d_image: torch.Tensor, cap: int | None = None, block_bytes: int = 0, tile_bytes: int = 0,
+                serial: bool = False, out: tuple | None = None, scratch: torch.Tensor | None = None):
+    """The walk of a device-resident image on the GPU (zscrc_device_walk),
+    asynchronous on the current stream: (span_off, span_len, res) int64 device
+    tensors -- `cap` entries each (default size // 8 + 1, the most an image
+    can hold) of which the first min(res[1], cap) are written, and res =
+    [result code, commits, end_off, longest span, shortest span, offset the
+    one-lane walk took over at or -1].  Equal to walk() of the same bytes.
+    out: preallocated (span_off, span_len, res) to write into; scratch: a
+    16-byte aligned uint8 tensor of walk_scratch_bytes() bytes (default: the
+    library's own, stream-ordered)."""
+    size = d_image.numel() * d_image.element_size()
+    dev = d_image.device
+    if cap is None:
+        cap = size // 8 + 1
+    if out is None:
+        out = (torch.empty(max(cap, 1), dtype=torch.int64, device=dev),
+               torch.empty(max(cap, 1), dtype=torch.int64, device=dev),
+               torch.empty(WALK_RES_WORDS, dtype=torch.int64, device=dev))
+    off, ln, res = out
+    assert off.numel() >= cap and ln.numel() >= cap and res.numel() >= WALK_RES_WORDS
+    opts = WalkOpts(block_bytes, tile_bytes)
+    with torch.cuda.device(dev):
+        check(lib().zscrc_device_walk(
+            d_image.data_ptr(), size, off.data_ptr(), ln.data_ptr(), cap, res.data_ptr(),
+            None if scratch is None else scratch.data_ptr(), ctypes.byref(opts), WALK_SERIAL if serial else 0,
+            torch.cuda.current_stream(dev).cuda_stream), "zscrc_device_walk")
+    return off, ln, res
+
+
+def verify_device_image(d_image: torch.Tensor, kind: int = ACTIVE) -> dict:
+    """verify_image() for a device-resident image (zscrc_device_verify_image):
+    the walk and every commit CRC on the GPU, only the header (and a packed
+    file's few locating words) copied to the host.  Synchronous."""
+    size = d_image.numel() * d_image.element_size()
+    rep = Report()
+    with torch.cuda.device(d_image.device):
+        check(lib().zscrc_device_verify_image(d_image.data_ptr(), size, kind, ctypes.byref(rep),
+                                              torch.cuda.current_stream(d_image.device).cuda_stream),
+              "zscrc_device_verify_image")
+    return rep.as_dict()
+
+
 def verify_commits(d_image: torch.Tensor, span_off: torch.Tensor, span_len: torch.Tensor,
                    seed: torch.Tensor | None = None, max_len: int | None = None):
     """Device-resident commit verification: (crc, status) int32 tensors;
