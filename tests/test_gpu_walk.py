@@ -2,9 +2,10 @@
 zscrc_device_verify_image against the host walk / zscrc_zs_verify_image on
 the same bytes: spans, count, result code and end offset equal, at the default
 geometry and at blocks / tiles small enough that every boundary case occurs
-inside a few KiB."""
+inside a few KiB; the well-formed, boundary, continuation, cap and scratch
+tests at every other number of slots per tile too (tests/walk_images.py,
+NEW_GEOMETRIES).  Images of several default blocks: tests/test_gpu_walk_scale.py."""
 import random
-import struct
 
 import numpy as np
 import pytest
@@ -13,6 +14,8 @@ import torch
 from oracle import zs_format as zf
 from tests import fuzzlib
 from tests.test_format_oracle import UUID, build_active
+from tests.walk_images import (NEW_GEOMETRIES, NEW_GEOMETRY_IDS, Img, boundary_cases, long_commit,  # noqa: F401
+                               long_key, short_commit, unaligned_image)
 from zeroskip_amd import zsfile
 
 pytestmark = pytest.mark.gpu
@@ -21,10 +24,12 @@ pytestmark = pytest.mark.gpu
 OPTSETS = [(0, 0), (64, 64), (512, 64), (4096, 512)]
 OPT_IDS = ["default", "b64_t64", "b512_t64", "b4096_t512"]
 SMALL = OPTSETS[1:]
+# with every other number of slots per tile, block == tile and one block for the whole image
+GEOMETRIES = OPTSETS + NEW_GEOMETRIES
+GEOMETRY_IDS = OPT_IDS + NEW_GEOMETRY_IDS
 U64_MAX = (1 << 64) - 1
 PAD = 4096
 CANARY = 0xA5
-T_2ND = zf.REC_2ND_HALF
 
 
 def _dev(img: bytes, dev) -> torch.Tensor:
@@ -59,151 +64,13 @@ def _same(img: bytes, d, block, tile, serial=False):
     return r
 
 
-# ------------------------------------------------------------ crafted images
-def short_commit(span_len=0, final=False):
-    return zf.be64(((zf.REC_FINAL if final else zf.REC_COMMIT) << 56) | (span_len << 32))
-
-
-def long_commit(span_len):
-    return zf.be64(zf.REC_LONG_COMMIT << 56) + zf.be64(span_len) + zf.be64(T_2ND << 56)
-
-
-def long_key(key: bytes):
-    kbuflen = 24 + zf.rup8(len(key))
-    return zf.be64(zf.REC_LONG_KEY << 56) + zf.be64(len(key)) + zf.be64(kbuflen) + key + \
-        bytes(kbuflen - 24 - len(key))
-
-
-class Img:
-    """Records laid one after another from the header; pad_to() fills with
-    delete records (and 8-byte commits) up to a wanted offset."""
-
-    def __init__(self):
-        self.b = bytearray(zf.header_bytes(UUID, 1, 1))
-
-    def __len__(self):
-        return len(self.b)
-
-    def add(self, rec: bytes) -> int:
-        at = len(self.b)
-        self.b += rec
-        return at
-
-    def pad_to(self, off: int):
-        assert off >= len(self.b) and off % 8 == 0
-        while len(self.b) < off:
-            gap = off - len(self.b)
-            if gap in (8, 16, 32):
-                self.b += short_commit(0)
-            else:
-                self.b += zf.delete_record(bytes([0x41]) * min(gap - 24, 4096))
-
-    def next_at(self, mod: int, rem: int, least: int = 0) -> int:
-        """Pad to the next offset == rem (mod `mod`) that leaves `least` bytes
-        of ordinary records before it; returns it."""
-        self.add(zf.key_record(b"k" * 9) + zf.value_record(b"v" * 21))
-        off = len(self.b) + least
-        off += (rem - off) % mod
-        self.pad_to(off)
-        return off
-
-    def image(self) -> bytes:
-        return bytes(self.b)
-
-
-def boundary_cases(B: int, T: int):
-    """[(name, image)] against tile T and block B; each case is checked here
-    to be what its name says, before any GPU work."""
-    out = []
-
-    im = Img()
-    a = im.next_at(T, T - 8)
-    im.add(short_commit(a - 40))
-    b = im.next_at(T, 0)
-    im.add(short_commit(8))
-    assert a % T == T - 8 and b % T == 0
-    out.append(("short_commit_last_and_first_slot", im.image()))
-
-    im = Img()
-    a = im.next_at(T, T - 8)
-    im.add(long_commit(a - 40))
-    b = im.next_at(B, B - 16)
-    im.add(long_commit(100))
-    im.add(zf.key_record(b"after") + zf.value_record(b"x" * 50) + short_commit(8))
-    assert a // T != (a + 23) // T and b // B != (b + 23) // B
-    out.append(("long_commit_straddles_tile_and_block", im.image()))
-
-    im = Img()
-    a = im.next_at(B, B - 8)
-    im.add(zf.key_record(b"K" * 40) + zf.value_record(b"V" * 70) + short_commit(16))
-    voff = struct.unpack(">Q", im.b[a:a + 8])[0] & 0xFFFFFFFF
-    assert a % B == B - 8 and (a + voff) // B == a // B + 1
-    out.append(("key_header_last_slot_of_block", im.image()))
-
-    im = Img()
-    a = im.next_at(B, B - 8)
-    im.add(long_key(b"L" * 33) + zf.value_record(b"W" * 9) + short_commit(0))
-    b = im.next_at(T, T - 16)
-    im.add(long_key(b"M" * 8) + zf.value_record(b"") + short_commit(24))
-    assert (a + 16) // B == a // B + 1 and (b + 16) // T == b // T + 1
-    out.append(("long_key_header_straddles", im.image()))
-
-    im = Img()
-    im.add(zf.key_record(b"big") + zf.value_record(bytes(range(256)) * ((2 * B + 300) // 256 + 1)))
-    a = im.add(short_commit(64))
-    im.add(zf.key_record(b"tail") + zf.value_record(b"t") + short_commit(8))
-    assert 40 // B == 0 and a // B >= 2  # the walk enters no block in between
-    out.append(("value_longer_than_two_blocks", im.image()))
-
-    im = Img()
-    im.next_at(B, B - 8)
-    im.add(short_commit(32))
-    assert len(im) % B == 0
-    out.append(("ends_on_block_boundary", im.image()))
-
-    im = Img()
-    im.next_at(T, 8)
-    a = im.add(short_commit(16, final=True))
-    im.add(zf.key_record(b"never") + zf.value_record(b"seen") + short_commit(8))
-    out.append(("final_mid_file", im.image()))
-    assert _host(im.image())[2:] == (zsfile.STOPPED, a)
-
-    hdr = zf.header_bytes(UUID, 1, 1)
-    out.append(("size_40", hdr))
-    h = _host(hdr)
-    assert (len(h[0]), h[2], h[3]) == (0, zsfile.END, 40)
-    for extra in range(1, 8):
-        img = hdr + bytes([4]) * extra
-        h = _host(img)
-        assert (len(h[0]), h[2], h[3]) == (0, zsfile.TRUNCATED, 40)
-        out.append((f"size_{40 + extra}", img))
-    return out
-
-
-def unaligned_image(prefix: bytes):
-    """prefix + a key record whose value offset points 28 bytes on, into the
-    key's own bytes, at a short value header placed there (offset = 4 mod 8);
-    the walk goes on at key + 52, where a commit word stands, and ends at
-    key + 60 = the image's end.  Returns (image, first unaligned offset)."""
-    assert len(prefix) % 8 == 0
-    K = len(prefix)
-    key = bytearray(64)
-    key[4:12] = zf.be64((zf.REC_VALUE << 56) | (8 << 32))
-    key[28:36] = short_commit(12)
-    rec = bytearray(zf.key_record(bytes(key)))
-    rec[0:8] = zf.be64((zf.REC_KEY << 56) | (64 << 40) | 28)
-    img = prefix + bytes(rec[:60])
-    assert (K + 28) % 8 == 4 and (K + 52) % 8 == 4
-    return img, K + 52
-
-
 @pytest.fixture(scope="module")
 def wellformed():
     return build_active(200, seed=11)
 
 
 # --------------------------------------------------------------------- tests
-@pytest.mark.parametrize("block,tile", OPTSETS, ids=OPT_IDS)
+@pytest.mark.parametrize("block,tile", GEOMETRIES, ids=GEOMETRY_IDS)
 def test_wellformed(gpu, wellformed, block, tile):
     img = wellformed
     assert len(img) > 16384  # more than one default tile: the three-launch path at the default too
@@ -263,13 +130,13 @@ def test_fuzz(fuzz_images, gpu):
 def test_boundaries(gpu, B, T):
     for name, img in boundary_cases(B, T):
         d = _dev(img, gpu)
-        for block, tile in OPTSETS:
+        for block, tile in GEOMETRIES:
             r = _same(img, d, block, tile)
             assert int(r[5]) == U64_MAX, name
             _same(img, d, block, tile, serial=True)
 
 
-@pytest.mark.parametrize("block,tile", OPTSETS, ids=OPT_IDS)
+@pytest.mark.parametrize("block,tile", GEOMETRIES, ids=GEOMETRY_IDS)
 def test_unaligned_continuation(gpu, wellformed, block, tile):
     img, first = unaligned_image(wellformed)
     hoff, hlen, hrc, hend = _host(img)
@@ -291,7 +158,7 @@ def _intact(whole: torch.Tensor, nbytes: int) -> bool:
     return bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all())
 
 
-@pytest.mark.parametrize("block,tile", OPTSETS, ids=OPT_IDS)
+@pytest.mark.parametrize("block,tile", GEOMETRIES, ids=GEOMETRY_IDS)
 def test_cap(gpu, wellformed, block, tile):
     img = wellformed
     hoff, hlen, hrc, hend = _host(img)
@@ -327,7 +194,7 @@ def test_serial_flag_on_wellformed(gpu, wellformed):
     _same(wellformed, _dev(wellformed, gpu), 0, 0, serial=True)
 
 
-@pytest.mark.parametrize("block,tile", OPTSETS, ids=OPT_IDS)
+@pytest.mark.parametrize("block,tile", GEOMETRIES, ids=GEOMETRY_IDS)
 def test_caller_scratch_fenced(gpu, wellformed, block, tile):
     img = wellformed
     hoff, hlen, hrc, hend = _host(img)
