@@ -8,6 +8,20 @@
  *
  * No HIP or torch types appear here: device pointers are plain pointers,
  * a stream is an opaque `void *` (a hipStream_t, NULL = default stream).
+ *
+ * Threads and streams.  Any entry point may be called from any host thread
+ * and on any stream, concurrently with any other; the special handles
+ * hipStreamLegacy (read as NULL) and hipStreamPerThread (one handle, another
+ * stream in every thread: never taken for the stream of an earlier call)
+ * included.  The library's per-device scratch is shared: calls that use it
+ * are enqueued under a lock and ordered across streams by an event, so
+ * concurrent callers get correct results but their scratch-using kernels run
+ * one call after another.  A handle object (zscrc_stream, zscrc_cpass, a
+ * device slot) belongs to one thread at a time.  The tuners (zscrc_set_*)
+ * are process-global and may change beside running calls: a call uses the
+ * values it reads, results never depend on them.  zscrc_release_cache() frees
+ * what other calls use: it must not run beside any other call.
+ * zscrc_last_error() is per thread.
  */
 #ifndef ZSCRC_H
 #define ZSCRC_H
@@ -515,7 +529,13 @@ typedef struct zscrc_cpass_spec {
     const uint32_t *d_file;       /* file id of each commit                      */
     uint64_t max_len;             /* bound on the span lengths (the host walk's);
                                    * create reads d_len back once and uses the
-                                   * true maximum, so a wrong value is harmless.
+                                   * larger of this and what it read.  The read
+                                   * is a blocking copy on the NULL stream: the
+                                   * true maximum of d_len is used only if d_len
+                                   * is complete at create -- lengths still being
+                                   * written on a non-blocking stream are read
+                                   * stale, and then max_len itself must hold (an
+                                   * over-stated one only costs time).
                                    * d_off / d_len must not change after create
                                    * (the image's bytes may)                      */
     size_t nspans;                /* raw spans                                   */

@@ -315,9 +315,24 @@ bool capturing(hipStream_t s)
     return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
 }
 
+/* Whether the handles a and b certainly name one stream.  hipStreamPerThread
+ * is one handle for a different stream in every host thread, so it never
+ * equals anything (its own earlier use included); hipStreamLegacy is the
+ * NULL stream under another name. */
+bool same_stream(hipStream_t a, hipStream_t b)
+{
+    if (a == hipStreamLegacy)
+        a = nullptr;
+    if (b == hipStreamLegacy)
+        b = nullptr;
+    return a == b && a != hipStreamPerThread;
+}
+
 int scratch_acquire(DevCtx *c, hipStream_t s)
 {
-    if (!c->last_valid || c->last_stream == s || capturing(s))
+    /* a wait on the stream's own event is harmless, so "not certainly the
+     * same stream" waits */
+    if (!c->last_valid || same_stream(c->last_stream, s) || capturing(s))
         return ZSCRC_OK;
     hipError_t e = hipStreamWaitEvent(s, c->last, 0);
     if (e != hipSuccess) {
@@ -653,13 +668,23 @@ int launch_commit_two_pass(DevCtx *c, zs::BatchDesc d, hipStream_t s)
 unsigned long long *verdict_slot(DevCtx *c, hipStream_t s)
 {
     const char *e = getenv("ZSCRC_VERDICT_MEMSET"); /* A/B: the fill launch */
-    if ((e && *e == '1') || capturing(s))
+    /* hipStreamPerThread names another stream in every host thread: a pair
+     * keyed by that handle would be shared by unordered streams */
+    if ((e && *e == '1') || s == hipStreamPerThread || capturing(s))
         return nullptr;
+    if (s == hipStreamLegacy) /* the NULL stream under another name */
+        s = nullptr;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (!c->vctr) {
+        /* every pair zeroed here, before any stream can use one (the pairs
+         * are 0 at rest, so nothing is zeroed per stream afterwards) */
         void *p = nullptr;
         if (hipMalloc(&p, 64 * 4 * 128) != hipSuccess)
             return nullptr;
+        if (hipMemset(p, 0, 64 * 4 * 128) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+            (void)hipFree(p);
+            return nullptr;
+        }
         c->vctr = static_cast<unsigned long long *>(p);
     }
     int k = 0;
@@ -667,10 +692,6 @@ unsigned long long *verdict_slot(DevCtx *c, hipStream_t s)
         ++k;
     if (k == c->vctr_n) {
         if (c->vctr_n == 64)
-            return nullptr;
-        /* the stream's four pairs zeroed on the stream itself, ahead of
-         * their first use (once per stream, no device-wide wait) */
-        if (hipMemsetAsync(c->vctr + 16 * 4 * k, 0, 4 * 128, s) != hipSuccess)
             return nullptr;
         c->vctr_stream[c->vctr_n++] = s;
     }

@@ -66,6 +66,7 @@ struct zscrc_cpass {
      * recorded there only then -- nothing extra per pass on one stream) */
     hipStream_t last_stream = nullptr;
     bool have_last = false;
+    bool last_per_thread = false; /* that pass ran on hipStreamPerThread and recorded `order` itself */
     hipEvent_t order = nullptr;
     hipEvent_t wait[2] = {};   /* what collect waits on: done[], or the caller's end event */
     bool pending[2] = {};
@@ -188,16 +189,20 @@ extern "C" int zscrc_cpass_create(zscrc_cpass **out, const zscrc_cpass_spec *spe
     }
     /* max_len selects which length classes the verdict launches (a range
      * that holds: the classes above it get no launch), so it must bound every
-     * span: the lengths are read back once here and the bound used is their
-     * true maximum -- a caller's under-stated max_len cannot leave long
-     * commits unchecked (an over-stated one would only cost time) */
+     * span: the lengths are read back once here and the bound used is the
+     * larger of their maximum and the caller's max_len -- an under-stated
+     * max_len cannot leave long commits unchecked (an over-stated one only
+     * costs time).  The copy is ordered after the NULL stream and blocking
+     * streams alone: lengths still being written on a non-blocking stream
+     * are read stale, and then the caller's max_len is the bound that holds
+     * (zscrc.h) */
     if (spec->n) {
         std::vector<uint64_t> lens(spec->n);
         if (hipMemcpy(lens.data(), spec->d_len, 8 * spec->n, hipMemcpyDeviceToHost) != hipSuccess) {
             cpass_free(p);
             return ZSCRC_EHIP;
         }
-        p->spec.max_len = *std::max_element(lens.begin(), lens.end());
+        p->spec.max_len = std::max<uint64_t>(spec->max_len, *std::max_element(lens.begin(), lens.end()));
     }
     *out = p;
     return ZSCRC_OK;
@@ -315,6 +320,7 @@ extern "C" int zscrc_cpass_set_row(zscrc_cpass *p, const zscrc_cpass_row_spec *r
 namespace {
 int cpass_enqueue(zscrc_cpass *p, hipStream_t s, hipEvent_t ev0, uint8_t **blk, uint8_t *host,
                   int64_t *d_row = nullptr, hipEvent_t done = nullptr);
+int cpass_enqueue_on(zscrc_cpass *p, hipStream_t s, uint8_t **blk, uint8_t *host, int64_t *d_row, hipEvent_t done);
 }
 
 extern "C" int zscrc_cpass_submit_row(zscrc_cpass *p, void *stream, void *start_event, void *end_event,
@@ -361,13 +367,38 @@ int cpass_submit(zscrc_cpass *p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, 
 int cpass_enqueue(zscrc_cpass *p, hipStream_t s, hipEvent_t ev0, uint8_t **blk, uint8_t *host, int64_t *d_row,
                   hipEvent_t done)
 {
-    if (p->have_last && s != p->last_stream &&
-        (hipEventRecord(p->order, p->last_stream) != hipSuccess || hipStreamWaitEvent(s, p->order, 0) != hipSuccess))
+    /* hipStreamPerThread names the calling thread's own stream: the previous
+     * pass's cannot be named from another thread, so a pass on it records
+     * `order` itself (at the end of this function) and the next pass always
+     * waits on that; every other handle is compared, hipStreamLegacy read as
+     * the NULL stream */
+    const hipStream_t key = s == hipStreamLegacy ? nullptr : s;
+    const bool same = p->have_last && !p->last_per_thread && key != hipStreamPerThread && key == p->last_stream;
+    if (p->have_last && !same &&
+        ((!p->last_per_thread && hipEventRecord(p->order, p->last_stream) != hipSuccess) ||
+         hipStreamWaitEvent(s, p->order, 0) != hipSuccess))
         return ZSCRC_EHIP;
-    p->last_stream = s;
-    p->have_last = true;
     if (ev0 && hipEventRecord(ev0, s) != hipSuccess)
         return ZSCRC_EHIP;
+    if (key != hipStreamPerThread) {
+        p->last_stream = key;
+        p->last_per_thread = false;
+        p->have_last = true;
+        return cpass_enqueue_on(p, s, blk, host, d_row, done);
+    }
+    const int rc = cpass_enqueue_on(p, s, blk, host, d_row, done);
+    if (hipEventRecord(p->order, s) == hipSuccess) {
+        p->last_stream = key;
+        p->last_per_thread = p->have_last = true;
+    } else { /* no event to order the next pass by: drain instead */
+        (void)hipStreamSynchronize(s);
+        p->have_last = false;
+    }
+    return rc;
+}
+
+int cpass_enqueue_on(zscrc_cpass *p, hipStream_t s, uint8_t **blk, uint8_t *host, int64_t *d_row, hipEvent_t done)
+{
     const zscrc_cpass_spec &sp = p->spec;
     uint8_t *b = p->dblk + p->blk_next * BLK, *other = p->dblk + (p->blk_next ^ 1) * BLK;
     p->blk_next ^= 1;

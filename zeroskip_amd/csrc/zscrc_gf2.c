@@ -1,6 +1,8 @@
 /* zscrc_gf2.c -- see zscrc_gf2.h. */
 #include "zscrc_gf2.h"
 
+#include <pthread.h>
+
 /* Multiply two reflected residues.  The loop walks a's coefficients from
  * x^0 (bit 31) upwards while b is multiplied by x at each step. */
 uint32_t zs_gf2_mul(uint32_t a, uint32_t b)
@@ -15,25 +17,23 @@ uint32_t zs_gf2_mul(uint32_t a, uint32_t b)
     return acc;
 }
 
-/* x^(8*2^k) mod P for k = 0..63, built once. */
+/* x^(8*2^k) mod P for k = 0..63, built once (pthread_once: any thread may
+ * be the first caller, the others wait for the finished table). */
 static uint32_t g_pow2[64];
-static int g_pow2_ready;
+static pthread_once_t g_pow2_once = PTHREAD_ONCE_INIT;
 
 static void pow2_init(void)
 {
-    if (g_pow2_ready)
-        return;
     uint32_t p = 0x00800000u; /* x^8 */
     for (int k = 0; k < 64; ++k) {
         g_pow2[k] = p;
         p = zs_gf2_mul(p, p);
     }
-    g_pow2_ready = 1;
 }
 
 uint32_t zs_gf2_xpow8n(uint64_t n)
 {
-    pow2_init();
+    pthread_once(&g_pow2_once, pow2_init);
     uint32_t r = 0x80000000u; /* x^0 */
     for (int k = 0; n; ++k, n >>= 1)
         if (n & 1)

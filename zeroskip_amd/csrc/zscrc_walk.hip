@@ -561,6 +561,18 @@ struct Scratch {
 };
 Scratch g_scratch[MAX_DEV];
 
+/* Whether the handles certainly name one stream: hipStreamPerThread is a
+ * different stream in every host thread (never equal, a wait on a stream's
+ * own event being harmless), hipStreamLegacy is the NULL stream. */
+bool same_stream(hipStream_t a, hipStream_t b)
+{
+    if (a == hipStreamLegacy)
+        a = nullptr;
+    if (b == hipStreamLegacy)
+        b = nullptr;
+    return a == b && a != hipStreamPerThread;
+}
+
 int launch(const Walk &w, unsigned flags, hipStream_t s)
 {
     if (serial_only(w, flags)) {
@@ -630,7 +642,7 @@ int zscrc_device_walk(const void *d_image, uint64_t image_size, uint64_t *d_span
         }
         sc.bytes = need;
     }
-    if (sc.last_valid && sc.last_stream != s && hipStreamWaitEvent(s, sc.last, 0) != hipSuccess)
+    if (sc.last_valid && !same_stream(sc.last_stream, s) && hipStreamWaitEvent(s, sc.last, 0) != hipSuccess)
         return ZSCRC_EHIP;
     place(sc.p);
     const int rc = launch(w, flags, s);
