@@ -488,6 +488,83 @@ int zscrc_device_walk(const void *d_image, uint64_t image_size,
 int zscrc_device_verify_image(const void *d_image, uint64_t image_size, int kind,
                               zscrc_zs_report *rep, void *stream);
 
+/* The walk over k images of one device buffer (the arena: a DB share kept
+ * resident, one file after another) in one call and four launches whatever k
+ * is; the output is what zscrc_device_verify_commits_* and zscrc_cpass_spec
+ * take for the arena: spans as offsets into it, and each commit's image. */
+/* One image of an arena: bytes [off, off + size) of the device buffer. */
+typedef struct zscrc_walk_image { uint64_t off, size; } zscrc_walk_image;
+#define ZSCRC_WALK_MULTI_MAX (1u << 20)   /* images per call */
+#define ZSCRC_WALK_ROW_WORDS 8
+#define ZSCRC_WALK_TOT_WORDS 4
+/* Bytes of scratch zscrc_device_walk_multi needs: 8 per 8-byte slot and 16 per
+ * block of every image of 40 bytes and more (each image is cut into slots and
+ * blocks from its own first byte), and 40 per image for its descriptor -- at
+ * most the sum over the images of 8 * ceil(size / 8) + 16 * blocks, plus
+ * 64 * (k + 1); appending an image never shrinks it.  0 = bad arguments:
+ * images NULL, k == 0 or above ZSCRC_WALK_MULTI_MAX, bad options, an image
+ * whose off + size wraps, more than 2^24 - 1 blocks over all images. */
+size_t zscrc_device_walk_multi_scratch_bytes(const zscrc_walk_image *images, size_t k,
+                                             const zscrc_walk_opts *opts);
+/* Asynchronous on `stream`.  images: a HOST array of k descriptors, the
+ * caller's to reuse on return -- the library copies them (32 bytes an image)
+ * into pinned staging of its own (one buffer per device, kept until
+ * zscrc_release_cache; a call waits on the host for the previous call's copy
+ * out of it, not for its walk) and from there to the device in stream order.
+ * Images may lie in the arena in any order and at any byte offset, overlap and
+ * repeat; one of fewer than 40 bytes (0 too) is legal and has no commits.
+ * d_span_off / d_span_len / d_span_img (device, cap entries): the commits of
+ * image 0 first, then image 1's ..., each image's in ascending offset order;
+ * d_span_off[i] is an offset into the ARENA (images[j].off + the offset
+ * zscrc_zs_walk gives for the image's bytes), d_span_len[i] its length,
+ * d_span_img[i] = j.  Entries at index >= cap are not written (cap 0: the
+ * three pointers may be NULL).
+ * d_rows (device, k * ZSCRC_WALK_ROW_WORDS words), row j, image-relative:
+ *   [0] zscrc_zs_walk's result code for image j alone with unlimited room
+ *       (END / STOPPED / TRUNCATED, never OVERFLOW);
+ *       (uint64_t)(int64_t)ZSCRC_EINVAL for size < 40
+ *   [1] its commits   [2] its end_off (0 for size < 40)
+ *   [3] its longest, [4] its shortest span length (0 when it has none)
+ *   [5] as zscrc_device_walk's res[5]: the offset in the image where a
+ *       one-lane walk took over, UINT64_MAX if none did
+ *   [6] the index of its first span in the output: the exclusive prefix sum
+ *       of [1], also for images without commits   [7] 0
+ * d_tot (device, ZSCRC_WALK_TOT_WORDS words): [0] ZSCRC_ZS_OVERFLOW if there
+ * are more commits than cap, else 0; [1] the commits of all images, counted
+ * past cap too; [2] the longest, [3] the shortest span of all (0 when there
+ * is none): what the _bounded and _verdict_range entry points want.
+ * flags must be 0 (no serial form: zscrc_device_walk and zscrc_zs_walk are the
+ * cross-checks).  scratch: 16-byte aligned device memory of
+ * zscrc_device_walk_multi_scratch_bytes bytes, or NULL for the library's
+ * per-device walk scratch (zscrc_device_walk's buffer and event ordering,
+ * grown to the largest need).  ZSCRC_EINVAL before any device call: d_arena,
+ * images, d_rows or d_tot NULL; k == 0 or above ZSCRC_WALK_MULTI_MAX; an image
+ * with off > arena_size or size > arena_size - off; cap > 0 with a span array
+ * NULL; flags != 0; misaligned scratch; bad options; more than 2^24 - 1 blocks
+ * over all images. */
+int zscrc_device_walk_multi(const void *d_arena, uint64_t arena_size,
+                            const zscrc_walk_image *images, size_t k,
+                            uint64_t *d_span_off, uint64_t *d_span_len, uint32_t *d_span_img, size_t cap,
+                            uint64_t *d_rows, uint64_t *d_tot, void *scratch,
+                            const zscrc_walk_opts *opts, unsigned flags, void *stream);
+/* zscrc_device_verify_image for k active or finalised images of an arena:
+ * reps[j] is, field for field, what zscrc_device_verify_image(d_arena +
+ * images[j].off, images[j].size, ZSCRC_ZS_ACTIVE, ...) reports for that image
+ * alone (first_bad: the index among that image's own commits).  Packed files
+ * have no walk and keep zscrc_device_verify_image.  Synchronous; returns 0
+ * (also when images are bad) or a negative status.  Launches, copies,
+ * allocations and synchronisations do not depend on k: one gather of the k
+ * headers and one copy of them to the host, one walk (a second one only when
+ * the images hold more than one commit per 64 bytes), one
+ * zscrc_device_verify_commits_bounded over the arena, one copy of the
+ * statuses and one of the rows.  Device memory for the call's duration: 28
+ * bytes per commit slot (the sum of size / 64 + 1 slots first), 136 bytes per
+ * image (descriptor, row, header); kept: the walk's library scratch, about
+ * the images' total size (zscrc_device_walk_multi). */
+int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size,
+                               const zscrc_walk_image *images, size_t k,
+                               zscrc_zs_report *reps, void *stream);
+
 /* `consistent` for one process / one GPU (zsdb_consistent,
  * src/zeroskip.c:1399-1407, and tool/cmd-consistent.c:23-49 are stubs in the
  * reference): every .zsdb / header / commit CRC of the DB directory,

@@ -100,6 +100,10 @@ SIGNATURES = {
     "zscrc_device_walk_scratch_bytes": (_sz, [_u64, _vp]),
     "zscrc_device_walk": (_int, [_vp, _u64, _vp, _vp, _sz, _vp, _vp, _vp, ctypes.c_uint, _vp]),
     "zscrc_device_verify_image": (_int, [_vp, _u64, _int, _vp, _vp]),
+    "zscrc_device_walk_multi_scratch_bytes": (_sz, [_vp, _sz, _vp]),
+    "zscrc_device_walk_multi": (_int, [_vp, _u64, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, ctypes.c_uint,
+                                       _vp]),
+    "zscrc_device_verify_images": (_int, [_vp, _u64, _vp, _sz, _vp, _vp]),
 }
 ABI_VERSION = 4  # include/zscrc.h ZSCRC_ABI_VERSION
 

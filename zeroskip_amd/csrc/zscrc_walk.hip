@@ -30,10 +30,16 @@
  * is bounded before it starts (doubling rounds = log2 of the tile's slots, at
  * most one hop per block, at most one step per slot in the serial loop).
  * Output positions come from prefix sums: ascending by offset, deterministic.
+ *
+ * zscrc_device_walk_multi (further down) is the same walk over many images of
+ * one device buffer in four launches, and zscrc_device_verify_images the
+ * verification of all of them on top of it.
  */
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <mutex>
 
 #include "../../include/zscrc.h"
@@ -195,13 +201,15 @@ __device__ __forceinline__ uint32_t exit_code(const Step &s, uint64_t k, uint64_
     return J_EXIT | (uint32_t)(k - b0);
 }
 
-__global__ __launch_bounds__(WG) void walk_table_kernel(Walk a)
+/* The table sweep of block `blk` of the image a describes, by one workgroup
+ * (walk_table_kernel, walk_multi_table_kernel). */
+__device__ __forceinline__ void table_sweep(const Walk &a, uint32_t blk)
 {
     __shared__ uint32_t s_p[TILE_SLOTS_MAX];   /* link (slot in the tile); a root points at itself */
     __shared__ uint32_t s_acc[TILE_SLOTS_MAX]; /* commits from the slot up to its link, exclusive */
     __shared__ uint32_t s_rj[TILE_SLOTS_MAX];  /* roots: J and C of the root itself */
     __shared__ uint32_t s_rc[TILE_SLOTS_MAX];
-    const uint64_t b0 = (uint64_t)blockIdx.x * a.bs;
+    const uint64_t b0 = (uint64_t)blk * a.bs;
     const uint64_t bend = b0 + a.bs < a.ns ? b0 + a.bs : a.ns;
     const uint32_t tiles = (uint32_t)((bend - b0 + a.ts - 1) / a.ts);
     for (uint32_t t = tiles; t-- > 0;) {
@@ -283,6 +291,8 @@ __global__ __launch_bounds__(WG) void walk_table_kernel(Walk a)
     }
 }
 
+__global__ __launch_bounds__(WG) void walk_table_kernel(Walk a) { table_sweep(a, blockIdx.x); }
+
 /* The plain loop of zscrc_zs_walk from (off, n), one lane; at most one step
  * per slot.  Spans go to index n onwards; mn / mx fold their lengths. */
 __device__ void serial_walk(const Walk &a, uint64_t off, uint64_t n, uint64_t mx, uint64_t mn, uint64_t took_over)
@@ -316,6 +326,27 @@ __device__ void serial_walk(const Walk &a, uint64_t off, uint64_t n, uint64_t mx
     /* the emit launch folds the blocks' lengths into [3] and [4] */
     a.res[4] = n ? mn : 0;
     a.res[5] = took_over;
+}
+
+/* serial_walk's loop for the many-image walk, which counts a tail in one
+ * launch and stores its spans in a later one: commit(offset, span length) for
+ * every commit passed; off ends where the walk does.  (serial_walk keeps its
+ * own copy: routed through this one, walk_serial_kernel and walk_chain_kernel
+ * take two registers more.) */
+template <class F>
+__device__ __forceinline__ int serial_loop(const Walk &a, uint64_t &off, F commit)
+{
+    for (uint64_t it = 0; it <= a.ns && off < a.size; ++it) {
+        const Step s = step(a.img, a.size, off);
+        if (s.kind == S_TRUNC)
+            return ZSCRC_ZS_TRUNCATED;
+        if (s.kind == S_STOP)
+            return ZSCRC_ZS_STOPPED;
+        if (s.kind == S_COMMIT)
+            commit(off, s.span);
+        off = s.next;
+    }
+    return ZSCRC_ZS_END;
 }
 
 __global__ __launch_bounds__(64) void walk_serial_kernel(Walk a)
@@ -519,6 +550,407 @@ __global__ __launch_bounds__(WG) void walk_emit_kernel(Walk a)
     }
 }
 
+/* What the many-image walk adds to a span on its way out: the arena offset of
+ * the image's first byte, the image's index and the totals' words. */
+struct Multi {
+    uint64_t add;
+    uint32_t *img;   /* d_span_img */
+    uint32_t j;
+    uint64_t *tot;
+};
+
+/* walk_emit_kernel's sweep of block `blk` of the image a describes for the
+ * many-image walk: the block's spans from index first_index onwards, offsets
+ * into the arena, the image's index beside them, lengths folded into the
+ * totals as well.  (walk_emit_kernel keeps its own copy: as an instance of
+ * this one it allocates a different number of registers.) */
+__device__ __forceinline__ void emit_sweep(const Walk &a, uint32_t blk, uint64_t first_index, const Multi &m)
+{
+    __shared__ uint32_t s_p[TILE_SLOTS_MAX]; /* link; after the doubling: 1 = a visited commit */
+    __shared__ uint32_t s_m[TILE_SLOTS_MAX]; /* 1 = the walk visits the slot */
+    __shared__ uint32_t s_scan[2][WG];
+    __shared__ uint32_t s_cur;               /* the walk's next slot in the block, NONE = it left */
+    __shared__ unsigned long long s_mx, s_mn;
+    const Entry en = a.entry[blk];
+    if (en.slot == NONE)
+        return;
+    const uint64_t b0 = (uint64_t)blk * a.bs;
+    const uint64_t bend = b0 + a.bs < a.ns ? b0 + a.bs : a.ns;
+    const uint32_t tiles = (uint32_t)((bend - b0 + a.ts - 1) / a.ts);
+    const uint32_t per = a.ts > WG ? a.ts / WG : 1; /* slots per thread of the scan, contiguous */
+    uint64_t base = first_index + en.base, mx = 0, mn = U64_MAX;
+    if (threadIdx.x == 0) {
+        s_cur = en.slot;
+        s_mx = 0;
+        s_mn = U64_MAX;
+    }
+    __syncthreads();
+    for (uint32_t t = 0; t < tiles; ++t) {
+        const uint32_t cur = s_cur;
+        if (cur == NONE)
+            break;
+        if (cur / a.ts != t) /* a record longer than the tile: the walk skips it */
+            continue;
+        const uint64_t t0 = b0 + (uint64_t)t * a.ts;
+        const uint64_t tend = t0 + a.ts < bend ? t0 + a.ts : bend;
+        __syncthreads(); /* every thread has read s_cur */
+        uint64_t w[SPT];
+#pragma unroll
+        for (uint32_t j = 0; j < SPT; ++j) {
+            const uint64_t k = t0 + threadIdx.x + j * WG;
+            w[j] = threadIdx.x + j * WG < a.ts && k < bend ? word_at(a.img, a.size, k << 3) : 0;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < SPT; ++j) {
+            const uint32_t i = threadIdx.x + j * WG;
+            if (i >= a.ts)
+                break;
+            const uint64_t k = t0 + i;
+            uint32_t p = i;
+            if (k < bend) {
+                const uint64_t n = link_of(step_w(a.img, a.size, k << 3, w[j]), tend);
+                if (n != U64_MAX)
+                    p = (uint32_t)(n - t0);
+            }
+            s_p[i] = p;
+            s_m[i] = i == cur - t * a.ts;
+        }
+        if (threadIdx.x == 0)
+            s_cur = NONE;
+        __syncthreads();
+        /* after round r the slots up to 2^(r+1) - 1 links from the entry are
+         * marked; a mark seen early only marks a later slot of the same chain */
+        for (uint32_t r = 0; r < a.rounds; ++r) {
+            uint32_t np[SPT];
+            int moved = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < SPT; ++j) {
+                const uint32_t i = threadIdx.x + j * WG;
+                if (i < a.ts) {
+                    const uint32_t p = s_p[i];
+                    if (s_m[i])
+                        s_m[p] = 1;
+                    np[j] = s_p[p];
+                    moved |= np[j] != p;
+                }
+            }
+            /* no link moved: the links reached their roots a round ago, so
+             * this round's marks were the last ones */
+            if (!__syncthreads_or(moved))
+                break;
+#pragma unroll
+            for (uint32_t j = 0; j < SPT; ++j) {
+                const uint32_t i = threadIdx.x + j * WG;
+                if (i < a.ts)
+                    s_p[i] = np[j];
+            }
+            __syncthreads();
+        }
+        /* visited slots: the commits among them, and where the walk goes
+         * from the last one (the one visited slot without a link) */
+        for (uint32_t i = threadIdx.x; i < a.ts; i += WG) {
+            uint32_t f = 0;
+            if (s_m[i]) {
+                const Step s = step(a.img, a.size, (t0 + i) << 3);
+                f = s.kind == S_COMMIT;
+                if (link_of(s, tend) == U64_MAX) {
+                    const uint64_t n = link_of(s, bend);
+                    s_cur = n == U64_MAX ? NONE : (uint32_t)(n - b0);
+                }
+            }
+            s_p[i] = f;
+        }
+        __syncthreads();
+        /* rank of each visited commit: prefix sum in slot order */
+        uint32_t mine = 0;
+        const uint32_t first = threadIdx.x * per;
+        if (first < a.ts)
+            for (uint32_t j = 0; j < per; ++j)
+                mine += s_p[first + j];
+        int cur_buf = 0;
+        s_scan[0][threadIdx.x] = mine;
+        __syncthreads();
+        for (uint32_t d = 1; d < WG; d <<= 1) {
+            uint32_t v = s_scan[cur_buf][threadIdx.x];
+            if (threadIdx.x >= d)
+                v += s_scan[cur_buf][threadIdx.x - d];
+            s_scan[cur_buf ^ 1][threadIdx.x] = v;
+            cur_buf ^= 1;
+            __syncthreads();
+        }
+        const uint32_t total = s_scan[cur_buf][WG - 1];
+        uint64_t rank = base + s_scan[cur_buf][threadIdx.x] - mine;
+        if (mine) {
+            for (uint32_t j = 0; j < per; ++j) {
+                if (!s_p[first + j])
+                    continue;
+                const uint64_t off = (t0 + first + j) << 3;
+                const Step s = step(a.img, a.size, off);
+                if (rank < a.cap) {
+                    a.off[rank] = m.add + (off - s.span);
+                    a.len[rank] = s.span;
+                    m.img[rank] = m.j;
+                }
+                mx = s.span > mx ? s.span : mx;
+                mn = s.span < mn ? s.span : mn;
+                ++rank;
+            }
+        }
+        base += total;
+        __syncthreads(); /* s_p, s_scan and s_cur are rewritten by the next tile */
+    }
+    if (mn != U64_MAX) {
+        atomicMax(&s_mx, (unsigned long long)mx);
+        atomicMin(&s_mn, (unsigned long long)mn);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_mn != U64_MAX) {
+        atomicMax(reinterpret_cast<unsigned long long *>(a.res + 3), s_mx);
+        atomicMin(reinterpret_cast<unsigned long long *>(a.res + 4), s_mn);
+        atomicMax(reinterpret_cast<unsigned long long *>(m.tot + 2), s_mx);
+        atomicMin(reinterpret_cast<unsigned long long *>(m.tot + 3), s_mn);
+    }
+}
+
+/* ------------------------------------------------- many images of one arena
+ * zscrc_device_walk_multi: the same walk over k images of one device buffer
+ * in four launches whatever k is.  Every image is cut into slots and blocks
+ * from its own first byte, so J, C and the entries of image j are exactly the
+ * single walk's for those bytes; the blocks (and slots) of all images are
+ * numbered one after another, image j's from blk0 (slot0) of its descriptor.
+ *
+ *   walk_multi_table_kernel  one workgroup per (image, block): table_sweep of
+ *                            that block; marks the block's entry as skipped
+ *   walk_multi_chain_kernel  one lane per image: the chain of walk_chain_kernel
+ *                            over its own J; row words [0] [1] [2] [5], the
+ *                            initial [3] [4]; past an unaligned next offset it
+ *                            only counts (serial_loop)
+ *   walk_multi_scan_kernel   one workgroup: row[6] = exclusive prefix sum of
+ *                            the counts, chunk by chunk with a carry; totals
+ *   walk_multi_emit_kernel   one workgroup per (image, block): emit_sweep from
+ *                            row[6]; and one lane per image that walks a
+ *                            counted tail again, storing its spans
+ */
+struct ImgD {
+    uint64_t off, size;   /* the image: bytes [off, off + size) of the arena */
+    uint64_t slot0;       /* its first slot of J and C */
+    uint32_t blk0;        /* its first block; blocks: blk0 of the next descriptor - blk0 */
+    uint32_t pad;
+};
+
+struct MWalk {
+    const uint8_t *arena;
+    const ImgD *im;       /* scratch: k + 1, the last one holds the totals */
+    uint64_t *tail_n;     /* scratch: k, the commits before a counted tail */
+    Entry *entry;         /* scratch: every image's blocks */
+    uint32_t *J, *C;      /* scratch: every image's slots */
+    uint32_t k, nblocks;
+    uint32_t bs, ts, rounds;
+    uint64_t *off, *len;
+    uint32_t *img;
+    uint64_t cap;
+    uint64_t *rows, *tot;
+};
+
+constexpr uint32_t SCAN_PER = 4;                /* the scan's counts per thread and chunk */
+constexpr uint64_t MULTI_MAX = ZSCRC_WALK_MULTI_MAX;
+constexpr int ROW = ZSCRC_WALK_ROW_WORDS;
+
+/* The image that block blk (< nblocks) belongs to: the last j with
+ * im[j].blk0 <= blk (images without blocks share their blk0 with the next
+ * one).  Uniform over the workgroup; at most 21 probes. */
+__device__ __forceinline__ uint32_t image_of(const MWalk &a, uint32_t blk)
+{
+    uint32_t lo = 0, hi = a.k; /* im[lo].blk0 <= blk < im[hi].blk0 */
+    for (int it = 0; it < 21 && hi - lo > 1; ++it) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.im[mid].blk0 <= blk)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+/* Image j as the single walk sees it; its spans go to the shared arrays. */
+__device__ __forceinline__ Walk view_of(const MWalk &a, uint32_t j)
+{
+    const ImgD d = a.im[j];
+    Walk w;
+    w.img = a.arena + d.off;
+    w.size = d.size;
+    w.ns = d.size / 8 + (d.size % 8 != 0);
+    w.bs = a.bs;
+    w.ts = a.ts;
+    w.rounds = a.rounds;
+    w.nblocks = a.im[j + 1].blk0 - d.blk0;
+    w.entry = a.entry + d.blk0;
+    w.J = a.J + d.slot0;
+    w.C = a.C + d.slot0;
+    w.off = a.off;
+    w.len = a.len;
+    w.cap = a.cap;
+    w.res = a.rows + (uint64_t)j * ROW;
+    return w;
+}
+
+__global__ __launch_bounds__(WG) void walk_multi_table_kernel(MWalk a)
+{
+    const uint32_t j = image_of(a, blockIdx.x);
+    const Walk w = view_of(a, j);
+    const uint32_t blk = blockIdx.x - a.im[j].blk0;
+    if (threadIdx.x == 0)
+        w.entry[blk].slot = NONE;
+    table_sweep(w, blk);
+}
+
+__global__ __launch_bounds__(WG) void walk_multi_chain_kernel(MWalk a)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
+    if (j >= a.k)
+        return;
+    const Walk w = view_of(a, (uint32_t)j);
+    uint64_t *row = w.res;
+    row[3] = 0;
+    row[7] = 0;
+    if (w.size < HDR) { /* no walk: zscrc_zs_walk's ZSCRC_EINVAL */
+        row[0] = (uint64_t)(int64_t)ZSCRC_EINVAL;
+        row[1] = row[2] = row[4] = 0;
+        row[5] = U64_MAX;
+        return;
+    }
+    uint64_t k = HDR / 8, n = 0, end = 0;
+    int rc = -1; /* -1: the chain goes on */
+    uint64_t unaligned = U64_MAX;
+    for (uint64_t hop = 0; hop <= w.nblocks; ++hop) {
+        if (k >= w.ns) {
+            rc = ZSCRC_ZS_END;
+            end = w.size;
+            break;
+        }
+        const uint64_t b = k / w.bs, b0 = b * w.bs;
+        w.entry[b].slot = (uint32_t)(k - b0);
+        w.entry[b].base = n;
+        const uint32_t jj = w.J[k];
+        n += w.C[k];
+        if (!(jj & J_EXIT)) {
+            k = b0 + jj;
+            continue;
+        }
+        const uint64_t e = (b0 + (jj & ~J_EXIT)) << 3;
+        const Step s = step(w.img, w.size, e);
+        if (s.kind == S_TRUNC || s.kind == S_STOP) {
+            rc = s.kind == S_TRUNC ? ZSCRC_ZS_TRUNCATED : ZSCRC_ZS_STOPPED;
+            end = e;
+            break;
+        }
+        if (s.next & 7) {
+            unaligned = s.next;
+            break;
+        }
+        k = s.next >> 3;
+    }
+    a.tail_n[j] = n;
+    if (unaligned != U64_MAX) { /* the spans' positions are not known yet: count */
+        end = unaligned;
+        rc = serial_loop(w, end, [&n](uint64_t, uint64_t) { ++n; });
+    }
+    row[0] = (uint64_t)rc;
+    row[1] = n;
+    row[2] = end;
+    row[4] = n ? U64_MAX : 0;
+    row[5] = unaligned;
+}
+
+__global__ __launch_bounds__(WG) void walk_multi_scan_kernel(MWalk a)
+{
+    __shared__ uint64_t s_scan[2][WG];
+    const uint32_t chunk = WG * SCAN_PER;
+    const uint32_t chunks = (a.k + chunk - 1) / chunk;
+    uint64_t carry = 0;
+    for (uint32_t c = 0; c < chunks; ++c) {
+        const uint64_t first = (uint64_t)c * chunk + threadIdx.x * SCAN_PER;
+        uint64_t cnt[SCAN_PER], mine = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < SCAN_PER; ++i) {
+            cnt[i] = first + i < a.k ? a.rows[(first + i) * ROW + 1] : 0;
+            mine += cnt[i];
+        }
+        int cur = 0;
+        s_scan[0][threadIdx.x] = mine;
+        __syncthreads();
+        for (uint32_t d = 1; d < WG; d <<= 1) {
+            uint64_t v = s_scan[cur][threadIdx.x];
+            if (threadIdx.x >= d)
+                v += s_scan[cur][threadIdx.x - d];
+            s_scan[cur ^ 1][threadIdx.x] = v;
+            cur ^= 1;
+            __syncthreads();
+        }
+        uint64_t at = carry + s_scan[cur][threadIdx.x] - mine;
+#pragma unroll
+        for (uint32_t i = 0; i < SCAN_PER; ++i) {
+            if (first + i < a.k)
+                a.rows[(first + i) * ROW + 6] = at;
+            at += cnt[i];
+        }
+        carry += s_scan[cur][WG - 1];
+        __syncthreads(); /* s_scan is rewritten by the next chunk */
+    }
+    if (threadIdx.x == 0) {
+        a.tot[0] = carry > a.cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : 0;
+        a.tot[1] = carry;
+        a.tot[2] = 0;
+        a.tot[3] = carry ? U64_MAX : 0; /* the emit launch folds the lengths into [2] and [3] */
+    }
+}
+
+/* Workgroup w: the emit sweep of block w (if there is one), then one lane per
+ * image of [w * WG, w * WG + WG) for the counted tails (if there are such
+ * images): a grid of max(blocks, ceil(k / WG)) workgroups. */
+__global__ __launch_bounds__(WG) void walk_multi_emit_kernel(MWalk a)
+{
+    if (blockIdx.x < a.nblocks) {
+        const uint32_t j = image_of(a, blockIdx.x);
+        const Walk w = view_of(a, j);
+        emit_sweep(w, blockIdx.x - a.im[j].blk0, w.res[6], Multi{a.im[j].off, a.img, j, a.tot});
+    }
+    const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
+    if (j >= a.k || a.rows[j * ROW + 5] == U64_MAX)
+        return;
+    const Walk w = view_of(a, (uint32_t)j);
+    const uint64_t add = a.im[j].off;
+    uint64_t off = w.res[5], n = w.res[6] + a.tail_n[j], mx = 0, mn = U64_MAX;
+    (void)serial_loop(w, off, [&](uint64_t at, uint64_t span) {
+        if (n < a.cap) {
+            a.off[n] = add + at - span;
+            a.len[n] = span;
+            a.img[n] = (uint32_t)j;
+        }
+        mx = span > mx ? span : mx;
+        mn = span < mn ? span : mn;
+        ++n;
+    });
+    if (mn != U64_MAX) {
+        atomicMax(reinterpret_cast<unsigned long long *>(w.res + 3), (unsigned long long)mx);
+        atomicMin(reinterpret_cast<unsigned long long *>(w.res + 4), (unsigned long long)mn);
+        atomicMax(reinterpret_cast<unsigned long long *>(a.tot + 2), (unsigned long long)mx);
+        atomicMin(reinterpret_cast<unsigned long long *>(a.tot + 3), (unsigned long long)mn);
+    }
+}
+
+/* The 40-byte headers of k images, one after another (zscrc_device_verify_images);
+ * zeros for an image of fewer than 40 bytes. */
+__global__ __launch_bounds__(WG) void walk_multi_headers_kernel(const uint8_t *arena, const ImgD *im, uint32_t k,
+                                                                uint8_t *out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x;
+    if (i >= (uint64_t)k * HDR)
+        return;
+    const ImgD d = im[i / HDR];
+    out[i] = d.size >= HDR ? arena[d.off + i % HDR] : 0;
+}
+
 /* ------------------------------------------------------------------ host */
 
 bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
@@ -558,6 +990,12 @@ struct Scratch {
     hipEvent_t last = nullptr;
     hipStream_t last_stream = nullptr;
     bool last_valid = false;
+    /* zscrc_device_walk_multi: pinned staging of the image descriptors on
+     * their way to the device, reused once its last copy has run (staged) */
+    void *pin = nullptr;
+    size_t pin_bytes = 0;
+    hipEvent_t staged = nullptr;
+    bool staged_valid = false;
 };
 Scratch g_scratch[MAX_DEV];
 
@@ -573,6 +1011,41 @@ bool same_stream(hipStream_t a, hipStream_t b)
     return a == b && a != hipStreamPerThread;
 }
 
+/* With sc.mu held: the library scratch grown to `need` bytes, and the stream
+ * made to wait for the buffer's last user on another stream. */
+int scratch_acquire(Scratch &sc, size_t need, hipStream_t s)
+{
+    if (sc.bytes < need) {
+        if (sc.p)
+            (void)hipFree(sc.p); /* waits for the device: no user is left */
+        sc.p = nullptr;
+        sc.bytes = 0;
+        sc.last_valid = false;
+        /* about the image's size: no slack on top */
+        if (hipMalloc(&sc.p, need) != hipSuccess) {
+            sc.p = nullptr;
+            return ZSCRC_ENOMEM;
+        }
+        sc.bytes = need;
+    }
+    if (sc.last_valid && !same_stream(sc.last_stream, s) && hipStreamWaitEvent(s, sc.last, 0) != hipSuccess)
+        return ZSCRC_EHIP;
+    return ZSCRC_OK;
+}
+
+/* With sc.mu held, after the launches (their status: rc): the event the
+ * buffer's next user waits for. */
+int scratch_done(Scratch &sc, hipStream_t s, int rc)
+{
+    if (!sc.last && hipEventCreateWithFlags(&sc.last, hipEventDisableTiming) != hipSuccess)
+        sc.last = nullptr;
+    sc.last_valid = sc.last && hipEventRecord(sc.last, s) == hipSuccess;
+    sc.last_stream = s;
+    if (!sc.last_valid && rc == ZSCRC_OK) /* no event to order the next user by: drain instead */
+        return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+    return rc;
+}
+
 int launch(const Walk &w, unsigned flags, hipStream_t s)
 {
     if (serial_only(w, flags)) {
@@ -582,6 +1055,100 @@ int launch(const Walk &w, unsigned flags, hipStream_t s)
         hipLaunchKernelGGL(walk_chain_kernel, dim3(1), dim3(WG), 0, s, w);
         hipLaunchKernelGGL(walk_emit_kernel, dim3((unsigned)w.nblocks), dim3(WG), 0, s, w);
     }
+    return hipGetLastError() == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+}
+
+/* The many-image walk's geometry and scratch layout: the descriptors (k + 1),
+ * the counts before a tail (k), then entries, J and C of all images. */
+struct Plan {
+    uint32_t bs, ts, rounds;
+    uint64_t nslots, nblocks;
+    size_t tail_at, entry_at, j_at, c_at, bytes;
+};
+
+uint64_t slots_of(uint64_t size) { return size < HDR ? 0 : size / 8 + (size % 8 != 0); }
+
+/* false = bad arguments.  check_arena: every image must lie inside
+ * arena_size bytes.  desc (k + 1 entries, may be NULL) receives the
+ * descriptors. */
+bool plan_multi(const zscrc_walk_image *images, size_t k, bool check_arena, uint64_t arena_size,
+                const zscrc_walk_opts *o, Plan *p, ImgD *desc)
+{
+    Walk g{};
+    if (!images || k == 0 || k > MULTI_MAX || !geometry(0, o, &g))
+        return false;
+    p->bs = g.bs;
+    p->ts = g.ts;
+    p->rounds = g.rounds;
+    uint64_t slots = 0, blocks = 0;
+    for (size_t j = 0; j < k; ++j) {
+        const uint64_t off = images[j].off, size = images[j].size;
+        if (size > U64_MAX - off) /* no arena holds it */
+            return false;
+        if (check_arena && (off > arena_size || size > arena_size - off))
+            return false;
+        if (desc)
+            desc[j] = ImgD{off, size, slots, (uint32_t)blocks, 0};
+        const uint64_t ns = slots_of(size);
+        slots += ns; /* < 2^61 each, k <= 2^20: no wrap */
+        blocks += (ns + g.bs - 1) / g.bs;
+        if (blocks > BLOCKS_MAX) /* one workgroup per block: a grid's threads must stay below 2^32 */
+            return false;
+    }
+    if (desc)
+        desc[k] = ImgD{0, 0, slots, (uint32_t)blocks, 0};
+    p->nslots = slots;
+    p->nblocks = blocks;
+    p->tail_at = (k + 1) * sizeof(ImgD);
+    p->entry_at = p->tail_at + ((k * 8 + 15) & ~(size_t)15);
+    p->j_at = p->entry_at + (size_t)blocks * sizeof(Entry);
+    p->c_at = p->j_at + (size_t)slots * 4;
+    p->bytes = p->c_at + (size_t)slots * 4;
+    return true;
+}
+
+/* With sc.mu held: the descriptors of `images` copied to d_desc (device,
+ * k + 1 entries) in stream order, through the pinned staging. */
+int stage_descriptors(Scratch &sc, const zscrc_walk_image *images, size_t k, const zscrc_walk_opts *o,
+                      void *d_desc, hipStream_t s)
+{
+    const size_t bytes = (k + 1) * sizeof(ImgD);
+    /* the staging's last copy must have run before its bytes change */
+    if (sc.staged_valid && hipEventSynchronize(sc.staged) != hipSuccess)
+        return ZSCRC_EHIP;
+    sc.staged_valid = false;
+    if (sc.pin_bytes < bytes) {
+        if (sc.pin)
+            (void)hipHostFree(sc.pin);
+        sc.pin = nullptr;
+        sc.pin_bytes = 0;
+        if (hipHostMalloc(&sc.pin, bytes, hipHostMallocDefault) != hipSuccess) {
+            sc.pin = nullptr;
+            return ZSCRC_ENOMEM;
+        }
+        sc.pin_bytes = bytes;
+    }
+    Plan p;
+    if (!plan_multi(images, k, false, 0, o, &p, static_cast<ImgD *>(sc.pin)))
+        return ZSCRC_EINVAL;
+    if (hipMemcpyAsync(d_desc, sc.pin, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+        return ZSCRC_EHIP;
+    if (!sc.staged && hipEventCreateWithFlags(&sc.staged, hipEventDisableTiming) != hipSuccess)
+        sc.staged = nullptr;
+    sc.staged_valid = sc.staged && hipEventRecord(sc.staged, s) == hipSuccess;
+    if (!sc.staged_valid) /* no event to wait for before the next fill: drain instead */
+        return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+    return ZSCRC_OK;
+}
+
+int launch_multi(const MWalk &m, hipStream_t s)
+{
+    const unsigned lanes = (m.k + WG - 1) / WG;
+    if (m.nblocks)
+        hipLaunchKernelGGL(walk_multi_table_kernel, dim3(m.nblocks), dim3(WG), 0, s, m);
+    hipLaunchKernelGGL(walk_multi_chain_kernel, dim3(lanes), dim3(WG), 0, s, m);
+    hipLaunchKernelGGL(walk_multi_scan_kernel, dim3(1), dim3(WG), 0, s, m);
+    hipLaunchKernelGGL(walk_multi_emit_kernel, dim3(m.nblocks > lanes ? m.nblocks : lanes), dim3(WG), 0, s, m);
     return hipGetLastError() == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
 }
 
@@ -628,34 +1195,175 @@ int zscrc_device_walk(const void *d_image, uint64_t image_size, uint64_t *d_span
         return ZSCRC_ENODEV;
     Scratch &sc = g_scratch[dev];
     std::lock_guard<std::mutex> lk(sc.mu);
-    const size_t need = scratch_bytes(w);
-    if (sc.bytes < need) {
-        if (sc.p)
-            (void)hipFree(sc.p); /* waits for the device: no user is left */
-        sc.p = nullptr;
-        sc.bytes = 0;
-        sc.last_valid = false;
-        /* about the image's size: no slack on top */
-        if (hipMalloc(&sc.p, need) != hipSuccess) {
-            sc.p = nullptr;
-            return ZSCRC_ENOMEM;
-        }
-        sc.bytes = need;
-    }
-    if (sc.last_valid && !same_stream(sc.last_stream, s) && hipStreamWaitEvent(s, sc.last, 0) != hipSuccess)
-        return ZSCRC_EHIP;
+    const int arc = scratch_acquire(sc, scratch_bytes(w), s);
+    if (arc)
+        return arc;
     place(sc.p);
-    const int rc = launch(w, flags, s);
-    if (!sc.last && hipEventCreateWithFlags(&sc.last, hipEventDisableTiming) != hipSuccess)
-        sc.last = nullptr;
-    sc.last_valid = sc.last && hipEventRecord(sc.last, s) == hipSuccess;
-    sc.last_stream = s;
-    if (!sc.last_valid && rc == ZSCRC_OK) /* no event to order the next user by: drain instead */
-        return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+    return scratch_done(sc, s, launch(w, flags, s));
+}
+
+size_t zscrc_device_walk_multi_scratch_bytes(const zscrc_walk_image *images, size_t k, const zscrc_walk_opts *opts)
+{
+    Plan p;
+    return plan_multi(images, k, false, 0, opts, &p, nullptr) ? p.bytes : 0;
+}
+
+int zscrc_device_walk_multi(const void *d_arena, uint64_t arena_size, const zscrc_walk_image *images, size_t k,
+                            uint64_t *d_span_off, uint64_t *d_span_len, uint32_t *d_span_img, size_t cap,
+                            uint64_t *d_rows, uint64_t *d_tot, void *scratch, const zscrc_walk_opts *opts,
+                            unsigned flags, void *stream)
+{
+    Plan p;
+    if (!d_arena || !d_rows || !d_tot || (cap && (!d_span_off || !d_span_len || !d_span_img)) || flags ||
+        (reinterpret_cast<uintptr_t>(scratch) & 15) || !plan_multi(images, k, true, arena_size, opts, &p, nullptr))
+        return ZSCRC_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV)
+        return ZSCRC_ENODEV;
+    Scratch &sc = g_scratch[dev];
+    std::lock_guard<std::mutex> lk(sc.mu);
+    if (!scratch) {
+        const int arc = scratch_acquire(sc, p.bytes, s);
+        if (arc)
+            return arc;
+    }
+    uint8_t *base = static_cast<uint8_t *>(scratch ? scratch : sc.p);
+    MWalk m{};
+    m.arena = static_cast<const uint8_t *>(d_arena);
+    m.im = reinterpret_cast<const ImgD *>(base);
+    m.tail_n = reinterpret_cast<uint64_t *>(base + p.tail_at);
+    m.entry = reinterpret_cast<Entry *>(base + p.entry_at);
+    m.J = reinterpret_cast<uint32_t *>(base + p.j_at);
+    m.C = reinterpret_cast<uint32_t *>(base + p.c_at);
+    m.k = (uint32_t)k;
+    m.nblocks = (uint32_t)p.nblocks;
+    m.bs = p.bs;
+    m.ts = p.ts;
+    m.rounds = p.rounds;
+    m.off = d_span_off;
+    m.len = d_span_len;
+    m.img = d_span_img;
+    m.cap = cap;
+    m.rows = d_rows;
+    m.tot = d_tot;
+    int rc = stage_descriptors(sc, images, k, opts, base, s);
+    if (!rc)
+        rc = launch_multi(m, s);
+    return scratch ? rc : scratch_done(sc, s, rc);
+}
+
+int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size, const zscrc_walk_image *images, size_t k,
+                               zscrc_zs_report *reps, void *stream)
+{
+    Plan p;
+    if (!d_arena || !reps || !plan_multi(images, k, true, arena_size, nullptr, &p, nullptr))
+        return ZSCRC_EINVAL;
+    memset(reps, 0, k * sizeof *reps);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV)
+        return ZSCRC_ENODEV;
+    /* device: descriptors, the rows, the totals, the gathered headers; host:
+     * the headers, then the rows */
+    const size_t desc_bytes = (k + 1) * sizeof(ImgD), rows_bytes = k * ROW * 8, hdr_bytes = k * HDR;
+    uint8_t *dfix = nullptr, *dspan = nullptr;
+    uint8_t *host = static_cast<uint8_t *>(malloc(rows_bytes > hdr_bytes ? rows_bytes : hdr_bytes));
+    uint32_t *st = nullptr;
+    uint64_t tot[ZSCRC_WALK_TOT_WORDS] = {};
+    size_t cap = 0;
+    int rc = host ? ZSCRC_OK : ZSCRC_ENOMEM;
+    if (!rc && hipMalloc(reinterpret_cast<void **>(&dfix), desc_bytes + rows_bytes + 64 + hdr_bytes) != hipSuccess)
+        rc = ZSCRC_ENOMEM;
+    uint64_t *drows = reinterpret_cast<uint64_t *>(dfix + desc_bytes), *dtot = drows + k * ROW;
+    uint8_t *dhdr = dfix + desc_bytes + rows_bytes + 64;
+    if (!rc) {
+        std::lock_guard<std::mutex> lk(g_scratch[dev].mu);
+        rc = stage_descriptors(g_scratch[dev], images, k, nullptr, dfix, s);
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(walk_multi_headers_kernel, dim3((unsigned)((hdr_bytes + WG - 1) / WG)), dim3(WG), 0, s,
+                           static_cast<const uint8_t *>(d_arena), reinterpret_cast<const ImgD *>(dfix), (uint32_t)k,
+                           dhdr);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(host, dhdr, hdr_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            rc = ZSCRC_EHIP;
+    }
+    if (!rc) {
+        for (size_t j = 0; j < k; ++j) {
+            const uint64_t size = images[j].size;
+            reps[j].header_rc = zscrc_zs_header_crc(host + j * HDR, size >= HDR ? HDR : size, &reps[j].header_stored,
+                                                    &reps[j].header_computed);
+            cap += (size_t)(size / 64) + 1;
+        }
+    }
+    /* most images hold far fewer commits than one per 8 bytes: a first walk
+     * with room for one per 64 bytes, and only if that overflows a second
+     * one with room for the count the first one found.  A commit slot:
+     * offset, length, image, CRC, status. */
+    uint64_t *doff = nullptr;
+    uint32_t *dimg = nullptr;
+    for (int pass = 0; !rc && pass < 2; ++pass) {
+        if (hipMalloc(reinterpret_cast<void **>(&dspan), cap * 28) != hipSuccess) {
+            rc = ZSCRC_ENOMEM;
+            break;
+        }
+        doff = reinterpret_cast<uint64_t *>(dspan);
+        dimg = reinterpret_cast<uint32_t *>(doff + 2 * cap);
+        rc = zscrc_device_walk_multi(d_arena, arena_size, images, k, doff, doff + cap, dimg, cap, drows, dtot, nullptr,
+                                     nullptr, 0, s);
+        if (!rc && (hipMemcpyAsync(tot, dtot, sizeof tot, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                    hipStreamSynchronize(s) != hipSuccess))
+            rc = ZSCRC_EHIP;
+        if (rc || tot[1] <= cap)
+            break;
+        (void)hipFree(dspan);
+        dspan = nullptr;
+        cap = (size_t)tot[1];
+    }
+    const size_t n = (size_t)tot[1];
+    if (!rc && n) {
+        uint32_t *dcrc = dimg + cap, *dst = dcrc + cap;
+        st = static_cast<uint32_t *>(malloc(n * 4));
+        if (!st)
+            rc = ZSCRC_ENOMEM;
+        if (!rc)
+            rc = zscrc_device_verify_commits_bounded(d_arena, arena_size, doff, doff + cap, nullptr, n, tot[2], dcrc,
+                                                     dst, s);
+        if (!rc && hipMemcpyAsync(st, dst, n * 4, hipMemcpyDeviceToHost, s) != hipSuccess)
+            rc = ZSCRC_EHIP;
+    }
+    if (!rc && (hipMemcpyAsync(host, drows, rows_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess))
+        rc = ZSCRC_EHIP;
+    if (!rc) {
+        const uint64_t *rows = reinterpret_cast<const uint64_t *>(host);
+        for (size_t j = 0; j < k; ++j) {
+            const uint64_t *row = rows + j * ROW;
+            zscrc_zs_report &r = reps[j];
+            r.walk_rc = (int)(int64_t)row[0];
+            r.n_commits = row[1];
+            r.end_off = row[2];
+            for (uint64_t i = 0; i < row[1]; ++i) {
+                if (st[row[6] + i] != 1) {
+                    if (r.n_bad == 0)
+                        r.first_bad = i;
+                    r.n_bad++;
+                }
+            }
+        }
+    }
+    if (dspan)
+        (void)hipFree(dspan);
+    if (dfix)
+        (void)hipFree(dfix);
+    free(st);
+    free(host);
     return rc;
 }
 
-/* zscrc_release_cache(): the walk's scratch, every device. */
+/* zscrc_release_cache(): the walk's scratch and descriptor staging, every device. */
 void zs_walk_release_cache(void)
 {
     int cur = -1;
@@ -663,17 +1371,27 @@ void zs_walk_release_cache(void)
     for (int d = 0; d < MAX_DEV; ++d) {
         Scratch &sc = g_scratch[d];
         std::lock_guard<std::mutex> lk(sc.mu);
-        if (!sc.p && !sc.last)
+        if (!sc.p && !sc.last && !sc.pin && !sc.staged)
             continue;
         (void)hipSetDevice(d);
         if (sc.p)
             (void)hipFree(sc.p);
         if (sc.last)
             (void)hipEventDestroy(sc.last);
+        if (sc.staged_valid)
+            (void)hipEventSynchronize(sc.staged);
+        if (sc.pin)
+            (void)hipHostFree(sc.pin);
+        if (sc.staged)
+            (void)hipEventDestroy(sc.staged);
         sc.p = nullptr;
         sc.bytes = 0;
         sc.last = nullptr;
         sc.last_valid = false;
+        sc.pin = nullptr;
+        sc.pin_bytes = 0;
+        sc.staged = nullptr;
+        sc.staged_valid = false;
     }
     if (cur >= 0)
         (void)hipSetDevice(cur);

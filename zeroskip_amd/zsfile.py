@@ -137,6 +137,85 @@ def verify_device_image(d_image: torch.Tensor, kind: int = ACTIVE) -> dict:
     return rep.as_dict()
 
 
+class WalkImage(ctypes.Structure):
+    """zscrc_walk_image (include/zscrc.h): bytes [off, off + size) of an arena."""
+    _fields_ = [("off", ctypes.c_uint64), ("size", ctypes.c_uint64)]
+
+
+WALK_ROW_WORDS = 8  # ZSCRC_WALK_ROW_WORDS
+WALK_TOT_WORDS = 4  # ZSCRC_WALK_TOT_WORDS
+WALK_MULTI_MAX = 1 << 20  # ZSCRC_WALK_MULTI_MAX
+
+
+def _walk_images(images):
+    """[(off, size)] as a zscrc_walk_image array (one entry's room for none)."""
+    images = list(images)
+    arr = (WalkImage * max(len(images), 1))()
+    for j, (off, size) in enumerate(images):
+        arr[j].off, arr[j].size = off, size
+    return arr, len(images)
+
+
+def walk_multi_scratch_bytes(images, block_bytes: int = 0, tile_bytes: int = 0) -> int:
+    """zscrc_device_walk_multi_scratch_bytes for images = [(off, size)];
+    0 = bad arguments."""
+    arr, k = _walk_images(images)
+    return lib().zscrc_device_walk_multi_scratch_bytes(arr, k, ctypes.byref(WalkOpts(block_bytes, tile_bytes)))
+
+
+def device_walk_multi(d_arena: torch.Tensor, images, cap: int | None = None, block_bytes: int = 0,
+                      tile_bytes: int = 0, out: tuple | None = None, scratch: torch.Tensor | None = None):
+    """The walk of the k images [(off, size)] of a device-resident arena in
+    one call (zscrc_device_walk_multi), asynchronous on the current stream:
+    (span_off, span_len, span_img, rows, tot) device tensors -- int64, int64,
+    int32 of `cap` entries each (default sum of size // 8 + 1), of which the
+    first min(tot[1], cap) are written: image 0's commits, then image 1's
+    ..., span_off as offsets into the arena; rows int64 (k, 8): [result code,
+    commits, end_off, longest span, shortest span, offset the one-lane walk
+    took over at or -1, index of the image's first span, 0], image-relative;
+    tot int64: [OVERFLOW or 0, commits of all images, longest span, shortest
+    span].  Each image's part equals walk() of its bytes.
+    out: preallocated (span_off, span_len, span_img, rows, tot); scratch: a
+    16-byte aligned uint8 tensor of walk_multi_scratch_bytes() bytes (default:
+    the library's own, stream-ordered)."""
+    size = d_arena.numel() * d_arena.element_size()
+    dev = d_arena.device
+    arr, k = _walk_images(images)
+    if cap is None:
+        cap = sum(arr[j].size // 8 + 1 for j in range(k))
+    if out is None:
+        out = (torch.empty(max(cap, 1), dtype=torch.int64, device=dev),
+               torch.empty(max(cap, 1), dtype=torch.int64, device=dev),
+               torch.empty(max(cap, 1), dtype=torch.int32, device=dev),
+               torch.empty((max(k, 1), WALK_ROW_WORDS), dtype=torch.int64, device=dev),
+               torch.empty(WALK_TOT_WORDS, dtype=torch.int64, device=dev))
+    off, ln, img, rows, tot = out
+    assert off.numel() >= cap and ln.numel() >= cap and img.numel() >= cap
+    assert rows.numel() >= k * WALK_ROW_WORDS and tot.numel() >= WALK_TOT_WORDS
+    opts = WalkOpts(block_bytes, tile_bytes)
+    with torch.cuda.device(dev):
+        check(lib().zscrc_device_walk_multi(
+            d_arena.data_ptr(), size, arr, k, off.data_ptr() or None, ln.data_ptr() or None, img.data_ptr() or None,
+            cap, rows.data_ptr(), tot.data_ptr(), None if scratch is None else scratch.data_ptr(),
+            ctypes.byref(opts), 0, torch.cuda.current_stream(dev).cuda_stream), "zscrc_device_walk_multi")
+    return off, ln, img, rows, tot
+
+
+def verify_device_images(d_arena: torch.Tensor, images) -> list:
+    """verify_device_image() for the k active or finalised images [(off,
+    size)] of a device-resident arena in one call (zscrc_device_verify_images):
+    a list of k report dicts, each equal to verify_device_image() of that
+    image's bytes alone.  Synchronous."""
+    size = d_arena.numel() * d_arena.element_size()
+    arr, k = _walk_images(images)
+    reps = (Report * max(k, 1))()
+    with torch.cuda.device(d_arena.device):
+        check(lib().zscrc_device_verify_images(d_arena.data_ptr(), size, arr, k, reps,
+                                               torch.cuda.current_stream(d_arena.device).cuda_stream),
+              "zscrc_device_verify_images")
+    return [reps[j].as_dict() for j in range(k)]
+
+
 def verify_commits(d_image: torch.Tensor, span_off: torch.Tensor, span_len: torch.Tensor,
                    seed: torch.Tensor | None = None, max_len: int | None = None):
     """Device-resident commit verification: (crc, status) int32 tensors;
