@@ -27,7 +27,7 @@ and events are at rest.  (Equal shapes do not make every missed ordering
 harmless: with handles compared for equality, the per-thread mode ran the
 threads' classify launches at once on the shared class lists and the device
 reported an illegal memory access -- the lists' scatter cursors are shared
-too.  same_stream() in zscrc_api.cpp / zscrc_walk.hip is the fix.)
+too.  same_stream() in zscrc_internal.h is the fix.)
 
 test_verdicts_on_seventy_streams: more streams than the 64 that get verdict
 counter pairs (verdict_slot's fallback).  test_cpass_create_beside_a_side_

@@ -15,7 +15,7 @@ from oracle import zs_format as zf
 from tests import fuzzlib
 from tests.test_format_oracle import UUID, build_active
 from tests.walk_images import (NEW_GEOMETRIES, NEW_GEOMETRY_IDS, Img, boundary_cases, long_commit,  # noqa: F401
-                               long_key, short_commit, unaligned_image)
+                               long_key, short_commit, unaligned_image, unaligned_tail_image)
 from zeroskip_amd import zsfile
 
 pytestmark = pytest.mark.gpu
@@ -188,6 +188,38 @@ def test_cap(gpu, wellformed, block, tile):
                                         torch.empty(zsfile.WALK_RES_WORDS, dtype=torch.int64, device=gpu)))
     r = _u64(res)
     assert int(r[0]) == zsfile.OVERFLOW and int(r[1]) == n and int(r[2]) == hend
+
+
+@pytest.mark.parametrize("block,tile", GEOMETRIES, ids=GEOMETRY_IDS)
+def test_unaligned_tail(gpu, wellformed, block, tile):
+    """A tail of four commits behind the first unaligned offset, the image's
+    shortest and longest span among them: the one-lane walk's stores, its `cap`
+    and its res[3] / res[4], which meet the emit launch's atomics there."""
+    img, first, n0 = unaligned_tail_image(wellformed)
+    hoff, hlen, hrc, hend = _host(img)
+    n = len(hoff)
+    assert (hrc, hend, n, n0) == (zsfile.END, len(img), 204, 200)
+    assert int(hlen.max()) == int(hlen[n0 + 2]) and int(hlen.min()) == int(hlen[n0 + 1])
+    d = _dev(img, gpu)
+    r = _same(img, d, block, tile)
+    assert int(r[5]) == first
+    for cap in (n0 - 1, n0, n0 + 1, n0 + 3, n0 + 4, n0 + 5):
+        fo, off = _fenced(cap * 8, gpu)
+        fl, ln = _fenced(cap * 8, gpu)
+        fr, res = _fenced(8 * zsfile.WALK_RES_WORDS, gpu)
+        zsfile.device_walk(d, cap=cap, block_bytes=block, tile_bytes=tile,
+                           out=(off.view(torch.int64), ln.view(torch.int64), res.view(torch.int64)))
+        r = _u64(res.view(torch.int64))
+        what = (cap, block, tile)
+        assert int(r[0]) == (zsfile.OVERFLOW if cap < n else zsfile.END), what
+        assert (int(r[1]), int(r[2]), int(r[5])) == (n, hend, first), what
+        assert int(r[3]) == int(hlen.max()) and int(r[4]) == int(hlen.min()), what
+        m = min(cap, n)
+        assert np.array_equal(_u64(off.view(torch.int64))[:m], hoff[:m]), what
+        assert np.array_equal(_u64(ln.view(torch.int64))[:m], hlen[:m]), what
+        # room past the last span (cap n + 1) stays untouched
+        assert bool((off[8 * m:] == CANARY).all()) and bool((ln[8 * m:] == CANARY).all()), what
+        assert _intact(fo, cap * 8) and _intact(fl, cap * 8) and _intact(fr, 8 * zsfile.WALK_RES_WORDS), what
 
 
 def test_serial_flag_on_wellformed(gpu, wellformed):

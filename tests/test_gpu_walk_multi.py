@@ -316,6 +316,24 @@ def test_caps(gpu):
     _check(_run(d, descs, cap=0, null_arrays=True), exp, "cap 0, no arrays")
 
 
+def test_unaligned_tail(gpu):
+    """A counted tail of four commits that holds its image's (and the arena's)
+    shortest and longest span, the image behind it taking its row[6] from the
+    tail's count; caps before, inside and at the end of the tail."""
+    un, first, n0 = wi.unaligned_tail_image(build_active(30, seed=2))
+    images = [build_active(6, seed=31), un, build_active(1, seed=35)]
+    d, descs, exp = _both(images, took_over={1: first}, dev=gpu)
+    rows, (total, mx, mn) = exp[3], exp[4]
+    assert n0 == 30 and total == 6 + 34 + 1
+    assert (int(rows[1][1]), int(rows[1][3]), int(rows[1][4])) == (34, mx, mn) and mn == 3
+    assert int(rows[2][6]) == int(rows[1][6]) + 34 == 40
+    tail = 6 + n0                                           # the index of the tail's first span
+    for block, tile in ((0, 0), (64, 64)):
+        _check(_run(d, descs, block=block, tile=tile), exp, ("whole", block))
+        for cap in (tail - 1, tail, tail + 1, tail + 3, tail + 4, total):
+            _check(_run(d, descs, cap=cap, block=block, tile=tile), exp, (cap, block))
+
+
 def test_order_repeat_overlap(gpu):
     images = [build_active(12, seed=41), build_active(5, seed=42), wi.dense_commit_image(500), build_active(1, seed=43)]
     buf, descs = _arena(images)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import walk_images as wi
+from tests.test_format_oracle import build_active
 from zeroskip_amd import zsfile
 
 
@@ -67,6 +68,24 @@ def test_dense_commit_image():
     off, ln, rc, end = wi.host_walk(img)
     assert len(off) == 1000 > len(img) // 64 + 1 == 626
     assert (ln == 32).all()
+
+
+@pytest.mark.parametrize("ntx,seed", [(200, 11), (30, 2)])
+def test_unaligned_tail_image(ntx, seed):
+    """The prefixes the GPU tests give it (tests/test_gpu_walk.py's wellformed,
+    tests/test_gpu_walk_multi.py's image): the tail holds the image's shortest
+    and its longest span, so res[3] / res[4] come from the one-lane walk."""
+    prefix = build_active(ntx, seed=seed)
+    poff, pln, _, _ = wi.host_walk(prefix)
+    img, first, before = wi.unaligned_tail_image(prefix)
+    off, ln, rc, end = wi.host_walk(img)
+    assert (rc, end) == (zsfile.END, len(img)) and end % 8 == 4
+    assert before == len(poff) == ntx and len(off) == before + 4
+    assert first == len(prefix) + 52 and first % 8 == 4
+    # build_active writes no transaction of 3 bytes or less, and none as long as the prefix
+    assert int(ln.min()) == 3 and int(pln.min()) > 3
+    assert int(ln.max()) == len(prefix) and int(pln.max()) < len(prefix)
+    assert [int(v) for v in ln[before:]] == [12, 3, len(prefix), 20]
 
 
 def test_huge_image_host_walk():

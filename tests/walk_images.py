@@ -184,6 +184,23 @@ def unaligned_image(prefix: bytes):
     return img, K + 52
 
 
+def unaligned_tail_image(prefix: bytes):
+    """unaligned_image(prefix) and, behind it, a short commit of span 3, a
+    delete record with an 8-byte key, a long commit whose span is len(prefix)
+    and a short commit of span 20: every record from the first unaligned
+    offset on starts at an offset = 4 mod 8, and the tail the one-lane walk
+    takes holds four commits of spans 12, 3, len(prefix) and 20.  Returns
+    (image, first unaligned offset, commits before the tail)."""
+    img, first = unaligned_image(prefix)
+    before = len(host_walk(prefix)[0])
+    img += short_commit(3) + zf.delete_record(b"8bytekey") + long_commit(len(prefix)) + short_commit(20)
+    assert len(img) == len(prefix) + 132
+    off, ln, rc, end = host_walk(img)
+    assert (rc, end, len(off)) == (zsfile.END, len(img), before + 4)
+    assert [int(v) for v in ln[before:]] == [12, 3, len(prefix), 20] and int(off[before] + ln[before]) == first
+    return img, first, before
+
+
 # ------------------------------------------------------ production-scale images
 def small_record_image(min_bytes: int, seed: int) -> bytes:
     """Transactions of 1-3 records (12-byte keys, values of 0-39 bytes), a

@@ -315,24 +315,11 @@ bool capturing(hipStream_t s)
     return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
 }
 
-/* Whether the handles a and b certainly name one stream.  hipStreamPerThread
- * is one handle for a different stream in every host thread, so it never
- * equals anything (its own earlier use included); hipStreamLegacy is the
- * NULL stream under another name. */
-bool same_stream(hipStream_t a, hipStream_t b)
-{
-    if (a == hipStreamLegacy)
-        a = nullptr;
-    if (b == hipStreamLegacy)
-        b = nullptr;
-    return a == b && a != hipStreamPerThread;
-}
-
 int scratch_acquire(DevCtx *c, hipStream_t s)
 {
     /* a wait on the stream's own event is harmless, so "not certainly the
      * same stream" waits */
-    if (!c->last_valid || same_stream(c->last_stream, s) || capturing(s))
+    if (!c->last_valid || zs::same_stream(c->last_stream, s) || capturing(s))
         return ZSCRC_OK;
     hipError_t e = hipStreamWaitEvent(s, c->last, 0);
     if (e != hipSuccess) {

@@ -2,6 +2,7 @@
 #ifndef ZSCRC_INTERNAL_H
 #define ZSCRC_INTERNAL_H
 
+#include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
 /* Global operator-table block (uint32 words), built on the host per device. */
@@ -17,6 +18,20 @@ enum {
 };
 
 namespace zs {
+
+/* Whether the handles a and b certainly name one stream (the library's
+ * scratch buffers are ordered between streams by events).  hipStreamPerThread
+ * is one handle for a different stream in every host thread, so it never
+ * equals anything (its own earlier use included); hipStreamLegacy is the
+ * NULL stream under another name. */
+inline bool same_stream(hipStream_t a, hipStream_t b)
+{
+    if (a == hipStreamLegacy)
+        a = nullptr;
+    if (b == hipStreamLegacy)
+        b = nullptr;
+    return a == b && a != hipStreamPerThread;
+}
 
 struct RecDesc;
 
