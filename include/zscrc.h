@@ -565,6 +565,57 @@ int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size,
                                const zscrc_walk_image *images, size_t k,
                                zscrc_zs_report *reps, void *stream);
 
+/* The record lister on the device: zscrc_zs_records (further down, with
+ * zscrc_zs_record and ZSCRC_ZS_DELETED) for an image that lives in device
+ * memory -- the list a repack starts from, without the image crossing PCIe.
+ * ACTIVE / FINALISED: the device walk's three launches (table, chain, emit) and
+ * its one-lane forms, stepping with zscrc_zs_records' own loop instead of
+ * zscrc_zs_walk's; the two loops differ on corrupt images (a commit whose span
+ * length exceeds its offset is skipped here and TRUNCATED there; a key record
+ * whose value offset lies inside its own header or key, or whose key length
+ * exceeds the bytes left, is TRUNCATED here and walked over there), and the
+ * result is always zscrc_zs_records'.  PACKED: the records in pointer-section
+ * order, three launches (a one-lane kernel that locates the two spans, one
+ * that finds the first pointer whose record does not parse, one that stores
+ * the records before it), no byte of the image copied to the host.
+ * Options, their limits and the scratch size for ACTIVE / FINALISED:
+ * zscrc_device_walk's.  PACKED needs 64 bytes.  0 = bad options or kind. */
+#define ZSCRC_RECORDS_RES_WORDS 12
+struct zscrc_zs_record;
+size_t zscrc_device_records_scratch_bytes(uint64_t image_size, int kind, const zscrc_walk_opts *opts);
+/* Asynchronous on `stream`.  d_recs (device, cap entries of 32 bytes): entry i
+ * for i < min(n, cap) is exactly what zscrc_zs_records writes for the same
+ * bytes; entries at index >= min(n, cap) are not written (cap 0: d_recs may be
+ * NULL).  d_res (device, ZSCRC_RECORDS_RES_WORDS words):
+ *   [0] zscrc_zs_records' return code for the same bytes and cap
+ *       (ZSCRC_ZS_OVERFLOW when there are more records than cap)
+ *   [1] the number of records n, all of them counted even past cap
+ *   [2] ACTIVE / FINALISED: the offset where the lister ended -- image_size, or
+ *       the offset of the record it stopped or truncated at; PACKED: the offset
+ *       of the pointer section (0 where the final commit does not locate it)
+ *   [3] the deletes, [4] the sum of key_len, [5] the sum of val_len (sums
+ *       modulo 2^64), [6] the longest key, [7] the longest value, over all n
+ *       records whatever cap is: what a device packer sizes its output by
+ *   [8] ACTIVE / FINALISED: the offset at which a one-lane loop took over (a
+ *       value offset that is no multiple of 8 leads to a record that starts at
+ *       no 8-byte slot), UINT64_MAX if none did, also when the whole list was
+ *       the one-lane loop's; PACKED: UINT64_MAX
+ *   [9] .. [11] 0
+ * PACKED, as the host: where the two spans or the pointer count do not check
+ * out, [0] is that code (ZSCRC_ZS_TRUNCATED) and [1] 0; where pointer i is the
+ * first whose record does not parse, [0] is TRUNCATED, [1] = i and only the
+ * records before it are stored and folded.
+ * flags: 0 or ZSCRC_WALK_SERIAL (the one-lane loop only; PACKED: one workgroup).
+ * scratch: 16-byte aligned device memory of zscrc_device_records_scratch_bytes
+ * bytes, or NULL for the walk's per-device library scratch (zscrc_device_walk:
+ * stream-ordered between calls, kept until zscrc_release_cache).
+ * ZSCRC_EINVAL before any device call: d_image or d_res NULL, cap > 0 with
+ * d_recs NULL, an unknown kind or flag, misaligned scratch, bad options,
+ * image_size < 40 (PACKED: < 56). */
+int zscrc_device_records(const void *d_image, uint64_t image_size, int kind,
+                         struct zscrc_zs_record *d_recs, size_t cap, uint64_t *d_res,
+                         void *scratch, const zscrc_walk_opts *opts, unsigned flags, void *stream);
+
 /* `consistent` for one process / one GPU (zsdb_consistent,
  * src/zeroskip.c:1399-1407, and tool/cmd-consistent.c:23-49 are stubs in the
  * reference): every .zsdb / header / commit CRC of the DB directory,
@@ -788,7 +839,8 @@ int zscrc_pack_abort(zscrc_packer *pk);
  * skipped; packed: the pointer section's order (zeroskip-packed.c:70-131).
  * Offsets are into the image; val_off == ZSCRC_ZS_DELETED marks a delete.
  * Returns ZSCRC_ZS_END (walked to the end; packed: ZSCRC_OK), STOPPED,
- * TRUNCATED, or OVERFLOW with *n_records = all records when cap is short. */
+ * TRUNCATED, or OVERFLOW with *n_records = all records when cap is short.
+ * For an image in device memory: zscrc_device_records (Part 3). */
 #define ZSCRC_ZS_DELETED UINT64_MAX
 typedef struct zscrc_zs_record {
     uint64_t key_off, key_len, val_off, val_len;

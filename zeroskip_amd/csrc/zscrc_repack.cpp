@@ -67,76 +67,19 @@
 #include <vector>
 
 #include "../../include/zscrc.h"
+#include "zscrc_records.h"
 
 namespace {
 
 constexpr uint64_t HDR = 40;
 constexpr size_t UUID_CHARS = 36;  /* UUID_STRLEN - 1, zeroskip-priv.h:53 */
 constexpr size_t DOTZSDB_SIZE = 61;
-enum { T_KEY = 1, T_VALUE = 2, T_COMMIT = 4, T_DELETED = 64, T_LONG = 32 };
+using zsrec::be64;
+using zsrec::record_at;
 
 double now_s()
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-inline uint64_t be64(const uint8_t *p)
-{
-    uint64_t v;
-    memcpy(&v, p, 8);
-    return __builtin_bswap64(v);
-}
-inline uint64_t rup8(uint64_t n) { return (n + 7) & ~7ull; }
-
-/* The key (and value) record at `off`; false if it is not one or does not
- * fit the image.  r.val_off = ZSCRC_ZS_DELETED for a delete record. */
-bool record_at(const uint8_t *img, uint64_t size, uint64_t off, zscrc_zs_record &r, uint64_t *next)
-{
-    if (off > size || size - off < 8)
-        return false;
-    const uint64_t room = size - off;
-    const uint64_t w = be64(img + off);
-    const unsigned t = (unsigned)(w >> 56);
-    if (t == T_KEY || t == (T_KEY | T_LONG)) {
-        uint64_t klen, voff;
-        if (t == T_KEY) {
-            klen = (w >> 40) & 0xFFFF;
-            voff = w & 0xFFFFFFFFull;
-        } else {
-            if (room < 24)
-                return false;
-            klen = be64(img + off + 8);
-            voff = be64(img + off + 16);
-        }
-        if (klen > room - 24 || voff > room || room - voff < 16 || voff < 24 + klen)
-            return false;
-        const uint64_t v = off + voff;
-        const uint64_t vw = be64(img + v);
-        const uint64_t vlen = (vw >> 56) == T_VALUE ? ((vw >> 32) & 0xFFFFFF) : be64(img + v + 8);
-        const uint64_t vroom = size - v - 16;
-        if (vlen > vroom || rup8(vlen) > vroom)
-            return false;
-        r.key_off = off + 24;
-        r.key_len = klen;
-        r.val_off = v + 16;
-        r.val_len = vlen;
-        *next = v + 16 + rup8(vlen);
-        return true;
-    }
-    if (t == T_DELETED || t == T_LONG) { /* REC_TYPE_LONG_DELETED = LONG | LONG */
-        if (room < 24)
-            return false;
-        const uint64_t klen = t == T_DELETED ? ((w >> 40) & 0xFFFF) : be64(img + off + 8);
-        if (klen > room - 24 || rup8(klen) > room - 24)
-            return false;
-        r.key_off = off + 24;
-        r.key_len = klen;
-        r.val_off = ZSCRC_ZS_DELETED;
-        r.val_len = 0;
-        *next = off + 24 + rup8(klen);
-        return true;
-    }
-    return false;
 }
 
 int memcmp_raw(const uint8_t *a, uint64_t la, const uint8_t *b, uint64_t lb)
@@ -364,14 +307,14 @@ extern "C" int zscrc_zs_records(const void *image, uint64_t size, int kind, zscr
         if (rc)
             return rc < 0 ? rc : (*n_records = 0, rc);
         /* pointer section: BE64 count, then BE64 record offsets */
-        const uint64_t poff = so[1], plen = sl[1];
-        const uint64_t count = plen >= 8 ? be64(img + poff) : 0;
-        if (plen < 8 || count > (plen - 8) / 8) {
+        const uint64_t poff = so[1];
+        uint64_t count;
+        if (!zsrec::pointer_count(img, poff, sl[1], &count)) {
             *n_records = 0;
             return ZSCRC_ZS_TRUNCATED;
         }
         for (uint64_t i = 0; i < count; ++i) {
-            if (!record_at(img, size, be64(img + poff + 8 + 8 * i), r, &next)) {
+            if (!record_at(img, size, zsrec::pointer_at(img, poff, i), r, &next)) {
                 rc = ZSCRC_ZS_TRUNCATED;
                 break;
             }
@@ -386,31 +329,21 @@ extern "C" int zscrc_zs_records(const void *image, uint64_t size, int kind, zscr
         return ZSCRC_EINVAL;
     uint64_t off = HDR;
     while (off < size) {
-        if (size - off < 8) {
+        /* the per-offset decision (zscrc_records.h) is the device lister's too */
+        const int what = zsrec::lister_step(img, size, off, r, &next);
+        if (what == zsrec::L_TRUNC) {
             rc = ZSCRC_ZS_TRUNCATED;
             break;
         }
-        const unsigned t = img[off];
-        if (t == T_COMMIT || t == (T_COMMIT | T_LONG)) {
-            const uint64_t rl = t == T_COMMIT ? 8 : 24;
-            if (size - off < rl) {
-                rc = ZSCRC_ZS_TRUNCATED;
-                break;
-            }
-            off += rl;
-            continue;
-        }
-        if (t != T_KEY && t != (T_KEY | T_LONG) && t != T_DELETED && t != T_LONG) {
+        if (what == zsrec::L_STOP) {
             rc = ZSCRC_ZS_STOPPED;
             break;
         }
-        if (!record_at(img, size, off, r, &next)) {
-            rc = ZSCRC_ZS_TRUNCATED;
-            break;
+        if (what == zsrec::L_RECORD) {
+            if (n < cap)
+                recs[n] = r;
+            ++n;
         }
-        if (n < cap)
-            recs[n] = r;
-        ++n;
         off = next;
     }
     *n_records = n;

@@ -37,6 +37,16 @@
  * walk's bodies on a Walk view of each image: table_sweep, chain_hops,
  * emit_sweep and serial_loop are written once, and the kernels of both walks
  * keep only what differs around them.
+ *
+ * The bodies take a step policy: what one iteration of the host loop does at
+ * an offset, which records are put out and what is folded over them.
+ * CommitWalk (zscrc_zs_walk's loop, the spans) is the policy of every kernel
+ * above; RecordList (zscrc_zs_records' loop, shared with the host through
+ * zscrc_records.h) makes zscrc_device_records the same three launches with
+ * 32-byte record entries as output.  The two host loops differ on corrupt
+ * images (the lister never looks at a commit's span length, the walk never at
+ * a key length), so neither can use the other's tables.  Packed images have no
+ * chain: records_packed_*_kernel parse the pointer section one pointer a thread.
  */
 #include <hip/hip_runtime.h>
 
@@ -47,6 +57,7 @@
 
 #include "../../include/zscrc.h"
 #include "zscrc_internal.h"
+#include "zscrc_records.h"
 
 namespace {
 
@@ -65,7 +76,10 @@ enum {
     T_KEY = 1, T_VALUE = 2, T_COMMIT = 4, T_FINAL = 16, T_DELETED = 64,
     T_LONG_KEY = 33, T_LONG_COMMIT = 36, T_LONG_FINAL = 48, T_LONG_DELETED_ALIAS = 32,
 };
-enum { S_ADV = 0, S_COMMIT = 1, S_TRUNC = 2, S_STOP = 3 };
+/* What a step finds: S_OUT = a record the walk puts out (the commit walk: a
+ * commit, S_COMMIT; the record lister: a key or delete record), S_ADV = one it
+ * only advances over; the shared bodies look at nothing else of a kind. */
+enum { S_ADV = 0, S_OUT = 1, S_COMMIT = S_OUT, S_TRUNC = 2, S_STOP = 3 };
 
 struct Step {
     uint32_t kind;  /* S_ADV / S_COMMIT: the walk goes on at next */
@@ -90,7 +104,7 @@ struct Walk {
     uint64_t nblocks;
     Entry *entry;         /* scratch: nblocks */
     uint32_t *J, *C;      /* scratch: ns each */
-    uint64_t *off, *len;
+    uint64_t *off, *len;  /* the spans (RecordList: off = the record entries, four words each; len unused) */
     uint64_t cap;
     uint64_t *res;
 };
@@ -175,27 +189,31 @@ __device__ Step step_w(const uint8_t *img, uint64_t size, uint64_t off, uint64_t
     return s;
 }
 
-__device__ __forceinline__ Step step(const uint8_t *img, uint64_t size, uint64_t off)
+/* The step of policy P at off < size, its word loaded here. */
+template <class P>
+__device__ __forceinline__ typename P::S step(const uint8_t *img, uint64_t size, uint64_t off)
 {
-    return step_w(img, size, off, word_at(img, size, off));
+    return P::step_w(img, size, off, word_at(img, size, off));
 }
 
 /* Where the walk goes from slot k (first slot of its block: b0, the block ends
  * before slot bend): the next slot when that is a slot of the same block
  * (the link the doubling follows), else NONE -- the record at k is then the
  * chain's last one in the block (its exit record). */
-__device__ __forceinline__ uint64_t link_of(const Step &s, uint64_t bend)
+template <class S>
+__device__ __forceinline__ uint64_t link_of(const S &s, uint64_t bend)
 {
-    if (s.kind > S_COMMIT || (s.next & 7))
+    if (s.kind > S_OUT || (s.next & 7))
         return U64_MAX;
     const uint64_t n = s.next >> 3;
     return n < bend ? n : U64_MAX;
 }
 
 /* J of an exit record at slot k of the block starting at b0. */
-__device__ __forceinline__ uint32_t exit_code(const Step &s, uint64_t k, uint64_t b0)
+template <class S>
+__device__ __forceinline__ uint32_t exit_code(const S &s, uint64_t k, uint64_t b0)
 {
-    if (s.kind <= S_COMMIT && !(s.next & 7)) {
+    if (s.kind <= S_OUT && !(s.next & 7)) {
         const uint64_t rel = (s.next >> 3) - b0;
         if (rel < J_EXIT)
             return (uint32_t)rel;
@@ -269,12 +287,171 @@ __device__ __forceinline__ void fold_lengths(uint64_t *w, uint64_t mx, uint64_t 
     atomicMin(reinterpret_cast<unsigned long long *>(w + 1), (unsigned long long)mn);
 }
 
+/* A step policy is what the shared bodies (table_sweep, chain_hops,
+ * emit_sweep, serial_loop, serial_walk, chain_walk) are instances of:
+ *   S          a step's result: kind, next, and what put() needs of the record
+ *   step_w     one iteration of the host loop at off < size, w = word_at(off);
+ *              reads nothing outside the image, next > off and next <= size
+ *   Acc        what a thread folds over the records it puts out
+ *   put        the S_OUT record at `at` as output entry `rank` (stored if
+ *              rank < cap), folded into acc either way
+ *   fold_init / fold_lds / folded / fold_out
+ *              a workgroup's Accs folded in FOLD words of LDS, then into the
+ *              result words: order-independent integer atomics only
+ *   finish     the result words, by the one lane that knows them
+ * CommitWalk is zscrc_zs_walk's loop (the commit spans), RecordList
+ * zscrc_zs_records' (the key and delete records). */
+struct CommitWalk {
+    using S = Step;
+    struct Acc {
+        uint64_t mx = 0, mn = U64_MAX;
+    };
+    static constexpr int FOLD = 2;
+    static __device__ __forceinline__ S step_w(const uint8_t *img, uint64_t size, uint64_t off, uint64_t w)
+    {
+        return ::step_w(img, size, off, w);
+    }
+    template <bool MULTI>
+    static __device__ __forceinline__ void put(const Walk &a, const Multi &m, uint64_t rank, uint64_t at, const S &s,
+                                               Acc &acc)
+    {
+        put_span<MULTI>(a, m, rank, at - s.span, s.span, acc.mx, acc.mn);
+    }
+    static __device__ __forceinline__ void fold_init(uint64_t *w)
+    {
+        w[0] = 0;
+        w[1] = U64_MAX;
+    }
+    static __device__ __forceinline__ void fold_lds(uint64_t *w, const Acc &acc)
+    {
+        if (acc.mn != U64_MAX)
+            fold_lengths(w, acc.mx, acc.mn);
+    }
+    static __device__ __forceinline__ bool folded(const uint64_t (&w)[FOLD]) { return w[1] != U64_MAX; }
+    template <bool MULTI>
+    static __device__ __forceinline__ void fold_out(const Walk &a, const Multi &m, uint64_t *w)
+    {
+        fold_lengths(a.res + 3, w[0], w[1]);
+        if constexpr (MULTI)
+            fold_lengths(m.tot + 2, w[0], w[1]);
+    }
+    /* the emit launch folds the blocks' lengths into [3] and [4] */
+    static __device__ __forceinline__ void finish(const Walk &a, int rc, uint64_t n, uint64_t end, const Acc &acc,
+                                                  uint64_t took_over)
+    {
+        a.res[0] = n > a.cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : (uint64_t)rc;
+        a.res[1] = n;
+        a.res[2] = end;
+        a.res[3] = acc.mx;
+        a.res[4] = n ? acc.mn : 0;
+        a.res[5] = took_over;
+    }
+};
+
+/* The record lister: Walk::off holds the zscrc_zs_record array (four words an
+ * entry), Walk::len nothing; res = ZSCRC_RECORDS_RES_WORDS words. */
+struct RStep {
+    uint32_t kind;
+    uint64_t next;
+    zscrc_zs_record rec;
+};
+
+struct RecordList {
+    using S = RStep;
+    struct Acc {
+        uint64_t del = 0, klen = 0, vlen = 0, kmax = 0, vmax = 0;
+    };
+    static constexpr int FOLD = 5;
+    /* zsrec::L_SKIP / L_RECORD / L_TRUNC / L_STOP are S_ADV / S_OUT / S_TRUNC / S_STOP */
+    static __device__ __forceinline__ S step_w(const uint8_t *img, uint64_t size, uint64_t off, uint64_t w)
+    {
+        static_assert(zsrec::L_SKIP == S_ADV && zsrec::L_RECORD == S_OUT && zsrec::L_TRUNC == S_TRUNC &&
+                          zsrec::L_STOP == S_STOP,
+                      "the lister's classes are the walk's");
+        S s;
+        s.next = off;
+        s.kind = (uint32_t)zsrec::lister_step_w(img, size, off, w, s.rec, &s.next);
+        return s;
+    }
+    static __device__ __forceinline__ void fold_rec(const zscrc_zs_record &r, Acc &acc)
+    {
+        acc.del += r.val_off == ZSCRC_ZS_DELETED;
+        acc.klen += r.key_len;
+        acc.vlen += r.val_len;
+        acc.kmax = r.key_len > acc.kmax ? r.key_len : acc.kmax;
+        acc.vmax = r.val_len > acc.vmax ? r.val_len : acc.vmax;
+    }
+    static __device__ __forceinline__ void store_rec(uint64_t *recs, uint64_t rank, const zscrc_zs_record &r)
+    {
+        uint64_t *o = recs + 4 * rank;
+        o[0] = r.key_off;
+        o[1] = r.key_len;
+        o[2] = r.val_off;
+        o[3] = r.val_len;
+    }
+    template <bool MULTI>
+    static __device__ __forceinline__ void put(const Walk &a, const Multi &, uint64_t rank, uint64_t, const S &s,
+                                               Acc &acc)
+    {
+        if (rank < a.cap)
+            store_rec(a.off, rank, s.rec);
+        fold_rec(s.rec, acc);
+    }
+    static __device__ __forceinline__ void fold_init(uint64_t *w)
+    {
+        for (int i = 0; i < FOLD; ++i)
+            w[i] = 0;
+    }
+    /* sums and maxima into w[0..4] (LDS or the result words [3..7]) */
+    static __device__ __forceinline__ void fold_words(uint64_t *w, uint64_t del, uint64_t klen, uint64_t vlen,
+                                                      uint64_t kmax, uint64_t vmax)
+    {
+        unsigned long long *u = reinterpret_cast<unsigned long long *>(w);
+        if (del)
+            atomicAdd(u, (unsigned long long)del);
+        if (klen) {
+            atomicAdd(u + 1, (unsigned long long)klen);
+            atomicMax(u + 3, (unsigned long long)kmax);
+        }
+        if (vlen) {
+            atomicAdd(u + 2, (unsigned long long)vlen);
+            atomicMax(u + 4, (unsigned long long)vmax);
+        }
+    }
+    static __device__ __forceinline__ void fold_lds(uint64_t *w, const Acc &acc)
+    {
+        fold_words(w, acc.del, acc.klen, acc.vlen, acc.kmax, acc.vmax);
+    }
+    static __device__ __forceinline__ bool folded(const uint64_t (&w)[FOLD]) { return (w[0] | w[1] | w[2]) != 0; }
+    template <bool MULTI>
+    static __device__ __forceinline__ void fold_out(const Walk &a, const Multi &, uint64_t *w)
+    {
+        fold_words(a.res + 3, w[0], w[1], w[2], w[3], w[4]);
+    }
+    /* the emit launch folds the blocks' records into [3] .. [7] */
+    static __device__ __forceinline__ void finish(const Walk &a, int rc, uint64_t n, uint64_t end, const Acc &acc,
+                                                  uint64_t took_over)
+    {
+        a.res[0] = n > a.cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : (uint64_t)rc;
+        a.res[1] = n;
+        a.res[2] = end;
+        a.res[3] = acc.del;
+        a.res[4] = acc.klen;
+        a.res[5] = acc.vlen;
+        a.res[6] = acc.kmax;
+        a.res[7] = acc.vmax;
+        a.res[8] = took_over;
+        a.res[9] = a.res[10] = a.res[11] = 0;
+    }
+};
+
 /* The table sweep of block `blk` of the image a describes, by one workgroup
- * (walk_table_kernel, walk_multi_table_kernel). */
+ * (walk_table_kernel, walk_multi_table_kernel, records_table_kernel). */
+template <class P>
 __device__ __forceinline__ void table_sweep(const Walk &a, uint32_t blk)
 {
     __shared__ uint32_t s_p[TILE_SLOTS_MAX];   /* link (slot in the tile); a root points at itself */
-    __shared__ uint32_t s_acc[TILE_SLOTS_MAX]; /* commits from the slot up to its link, exclusive */
+    __shared__ uint32_t s_acc[TILE_SLOTS_MAX]; /* S_OUT records from the slot up to its link, exclusive */
     __shared__ uint32_t s_rj[TILE_SLOTS_MAX];  /* roots: J and C of the root itself */
     __shared__ uint32_t s_rc[TILE_SLOTS_MAX];
     const uint64_t b0 = (uint64_t)blk * a.bs;
@@ -292,8 +469,8 @@ __device__ __forceinline__ void table_sweep(const Walk &a, uint32_t blk)
             const uint64_t k = t0 + i;
             uint32_t p = i, acc = 0, rj = 0, rc = 0;
             if (k < bend) {
-                const Step s = step_w(a.img, a.size, k << 3, w[j]);
-                const uint32_t cm = s.kind == S_COMMIT;
+                const typename P::S s = P::step_w(a.img, a.size, k << 3, w[j]);
+                const uint32_t cm = s.kind == S_OUT;
                 const uint64_t n = link_of(s, bend);
                 if (n == U64_MAX) {
                     rj = exit_code(s, k, b0);
@@ -355,19 +532,19 @@ __device__ __forceinline__ void table_sweep(const Walk &a, uint32_t blk)
     }
 }
 
-__global__ __launch_bounds__(WG) void walk_table_kernel(Walk a) { table_sweep(a, blockIdx.x); }
+__global__ __launch_bounds__(WG) void walk_table_kernel(Walk a) { table_sweep<CommitWalk>(a, blockIdx.x); }
 
-/* The plain loop of zscrc_zs_walk from off, one lane; at most one step per
- * slot.  commit(offset, span length) for every commit passed; off ends where
- * the walk does.  (The many-image walk counts a tail in one launch and stores
+/* The plain host loop (zscrc_zs_walk, or the policy's) from off, one lane; at
+ * most one step per slot.  out(offset, step) for every S_OUT record passed;
+ * off ends where the walk does.  (The many-image walk counts a tail in one launch and stores
  * its spans in a later one.)  This loop and chain_hops' set rc and break:
  * with returns inside them a step and a hop took 2-3 % longer. */
-template <class F>
-__device__ __forceinline__ int serial_loop(const Walk &a, uint64_t &off, F commit)
+template <class P, class F>
+__device__ __forceinline__ int serial_loop(const Walk &a, uint64_t &off, F out)
 {
     int rc = ZSCRC_ZS_END;
     for (uint64_t it = 0; it <= a.ns && off < a.size; ++it) {
-        const Step s = step(a.img, a.size, off);
+        const typename P::S s = step<P>(a.img, a.size, off);
         if (s.kind == S_TRUNC) {
             rc = ZSCRC_ZS_TRUNCATED;
             break;
@@ -376,34 +553,29 @@ __device__ __forceinline__ int serial_loop(const Walk &a, uint64_t &off, F commi
             rc = ZSCRC_ZS_STOPPED;
             break;
         }
-        if (s.kind == S_COMMIT)
-            commit(off, s.span);
+        if (s.kind == S_OUT)
+            out(off, s);
         off = s.next;
     }
     return rc;
 }
 
-/* The single walk's one-lane loop from (off, n): spans go to index n onwards,
- * and it writes the result words. */
+/* A single image's one-lane loop from (off, n): its output goes to index n
+ * onwards, and it writes the result words. */
+template <class P>
 __device__ void serial_walk(const Walk &a, uint64_t off, uint64_t n, uint64_t took_over)
 {
-    uint64_t mx = 0, mn = U64_MAX;
-    const int rc = serial_loop(a, off, [&](uint64_t at, uint64_t span) {
-        put_span<false>(a, Multi{}, n++, at - span, span, mx, mn);
+    typename P::Acc acc;
+    const int rc = serial_loop<P>(a, off, [&](uint64_t at, const typename P::S &s) {
+        P::template put<false>(a, Multi{}, n++, at, s, acc);
     });
-    a.res[0] = n > a.cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : (uint64_t)rc;
-    a.res[1] = n;
-    a.res[2] = off;
-    a.res[3] = mx;
-    /* the emit launch folds the blocks' lengths into [3] and [4] */
-    a.res[4] = n ? mn : 0;
-    a.res[5] = took_over;
+    P::finish(a, rc, n, off, acc, took_over);
 }
 
 __global__ __launch_bounds__(64) void walk_serial_kernel(Walk a)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0)
-        serial_walk(a, HDR, 0, U64_MAX);
+        serial_walk<CommitWalk>(a, HDR, 0, U64_MAX);
 }
 
 /* The chain of image a, one lane: k = J[k] from slot 5, one hop per block
@@ -411,6 +583,7 @@ __global__ __launch_bounds__(64) void walk_serial_kernel(Walk a)
  * n = the commits passed and end = the end offset; or -1 where the chain
  * reaches an offset that is no multiple of 8, unaligned (else U64_MAX), with n
  * = the commits before it: the one-lane loop goes on from there. */
+template <class P>
 __device__ __forceinline__ int chain_hops(const Walk &a, uint64_t &n, uint64_t &end, uint64_t &unaligned)
 {
     uint64_t k = HDR / 8;
@@ -433,7 +606,7 @@ __device__ __forceinline__ int chain_hops(const Walk &a, uint64_t &n, uint64_t &
             continue;
         }
         const uint64_t e = (b0 + (j & ~J_EXIT)) << 3;
-        const Step s = step(a.img, a.size, e);
+        const typename P::S s = step<P>(a.img, a.size, e);
         if (s.kind == S_TRUNC || s.kind == S_STOP) {
             rc = s.kind == S_TRUNC ? ZSCRC_ZS_TRUNCATED : ZSCRC_ZS_STOPPED;
             end = e;
@@ -448,7 +621,12 @@ __device__ __forceinline__ int chain_hops(const Walk &a, uint64_t &n, uint64_t &
     return rc;
 }
 
-__global__ __launch_bounds__(WG) void walk_chain_kernel(Walk a)
+/* A single image's chain launch, one workgroup: every entry marked as
+ * skipped, then one lane hops and writes the result words.  (a by value, as
+ * the kernel has it: by reference the commit instance came out three
+ * instructions longer than with this body written into walk_chain_kernel.) */
+template <class P>
+__device__ __forceinline__ void chain_walk(const Walk a)
 {
     for (uint64_t b = threadIdx.x; b < a.nblocks; b += WG)
         a.entry[b].slot = NONE;
@@ -456,32 +634,29 @@ __global__ __launch_bounds__(WG) void walk_chain_kernel(Walk a)
     if (threadIdx.x != 0)
         return;
     uint64_t n, end, unaligned;
-    const int rc = chain_hops(a, n, end, unaligned);
+    const int rc = chain_hops<P>(a, n, end, unaligned);
     if (unaligned != U64_MAX) {
-        serial_walk(a, unaligned, n, unaligned);
+        serial_walk<P>(a, unaligned, n, unaligned);
         return;
     }
-    a.res[0] = n > a.cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : (uint64_t)rc;
-    a.res[1] = n;
-    a.res[2] = end;
-    a.res[3] = 0;
-    a.res[4] = n ? U64_MAX : 0;
-    a.res[5] = U64_MAX;
+    P::finish(a, rc, n, end, typename P::Acc{}, U64_MAX);
 }
+
+__global__ __launch_bounds__(WG) void walk_chain_kernel(Walk a) { chain_walk<CommitWalk>(a); }
 
 /* The emit sweep of block `blk` of the image a describes, by one workgroup
  * (walk_emit_kernel, walk_multi_emit_kernel): the block's spans from index
  * first_index + the entry's base onwards, lengths folded into res[3], res[4].
  * MULTI, the many-image walk: offsets into the arena, the image's index
  * beside them, lengths folded into the totals as well (m; unused otherwise). */
-template <bool MULTI>
+template <class P, bool MULTI>
 __device__ __forceinline__ void emit_sweep(const Walk &a, uint32_t blk, uint64_t first_index, const Multi &m)
 {
-    __shared__ uint32_t s_p[TILE_SLOTS_MAX]; /* link; after the doubling: 1 = a visited commit */
+    __shared__ uint32_t s_p[TILE_SLOTS_MAX]; /* link; after the doubling: 1 = a visited S_OUT record */
     __shared__ uint32_t s_m[TILE_SLOTS_MAX]; /* 1 = the walk visits the slot */
     __shared__ uint32_t s_scan[2][WG];
     __shared__ uint32_t s_cur;               /* the walk's next slot in the block, NONE = it left */
-    __shared__ uint64_t s_mm[2];             /* the workgroup's longest and shortest span */
+    __shared__ uint64_t s_mm[P::FOLD];       /* the workgroup's fold (the commit walk: longest and shortest span) */
     const Entry en = a.entry[blk];
     if (en.slot == NONE)
         return;
@@ -489,11 +664,11 @@ __device__ __forceinline__ void emit_sweep(const Walk &a, uint32_t blk, uint64_t
     const uint64_t bend = b0 + a.bs < a.ns ? b0 + a.bs : a.ns;
     const uint32_t tiles = (uint32_t)((bend - b0 + a.ts - 1) / a.ts);
     const uint32_t per = a.ts > WG ? a.ts / WG : 1; /* slots per thread of the scan, contiguous */
-    uint64_t base = first_index + en.base, mx = 0, mn = U64_MAX;
+    uint64_t base = first_index + en.base;
+    typename P::Acc acc;
     if (threadIdx.x == 0) {
         s_cur = en.slot;
-        s_mm[0] = 0;
-        s_mm[1] = U64_MAX;
+        P::fold_init(s_mm);
     }
     __syncthreads();
     for (uint32_t t = 0; t < tiles; ++t) {
@@ -515,7 +690,7 @@ __device__ __forceinline__ void emit_sweep(const Walk &a, uint32_t blk, uint64_t
             const uint64_t k = t0 + i;
             uint32_t p = i;
             if (k < bend) {
-                const uint64_t n = link_of(step_w(a.img, a.size, k << 3, w[j]), tend);
+                const uint64_t n = link_of(P::step_w(a.img, a.size, k << 3, w[j]), tend);
                 if (n != U64_MAX)
                     p = (uint32_t)(n - t0);
             }
@@ -558,8 +733,8 @@ __device__ __forceinline__ void emit_sweep(const Walk &a, uint32_t blk, uint64_t
         for (uint32_t i = threadIdx.x; i < a.ts; i += WG) {
             uint32_t f = 0;
             if (s_m[i]) {
-                const Step s = step(a.img, a.size, (t0 + i) << 3);
-                f = s.kind == S_COMMIT;
+                const typename P::S s = step<P>(a.img, a.size, (t0 + i) << 3);
+                f = s.kind == S_OUT;
                 if (link_of(s, tend) == U64_MAX) {
                     const uint64_t n = link_of(s, bend);
                     s_cur = n == U64_MAX ? NONE : (uint32_t)(n - b0);
@@ -581,24 +756,139 @@ __device__ __forceinline__ void emit_sweep(const Walk &a, uint32_t blk, uint64_t
                 if (!s_p[first + j])
                     continue;
                 const uint64_t off = (t0 + first + j) << 3;
-                const Step s = step(a.img, a.size, off);
-                put_span<MULTI>(a, m, rank++, off - s.span, s.span, mx, mn);
+                const typename P::S s = step<P>(a.img, a.size, off);
+                P::template put<MULTI>(a, m, rank++, off, s, acc);
             }
         }
         base += total;
         __syncthreads(); /* s_p, s_scan and s_cur are rewritten by the next tile */
     }
-    if (mn != U64_MAX)
-        fold_lengths(s_mm, mx, mn);
+    P::fold_lds(s_mm, acc);
     __syncthreads();
-    if (threadIdx.x == 0 && s_mm[1] != U64_MAX) {
-        fold_lengths(a.res + 3, s_mm[0], s_mm[1]);
-        if constexpr (MULTI)
-            fold_lengths(m.tot + 2, s_mm[0], s_mm[1]);
-    }
+    const bool any = P::folded(s_mm);
+    if (threadIdx.x == 0 && any)
+        P::template fold_out<MULTI>(a, m, s_mm);
 }
 
-__global__ __launch_bounds__(WG) void walk_emit_kernel(Walk a) { emit_sweep<false>(a, blockIdx.x, 0, Multi{}); }
+__global__ __launch_bounds__(WG) void walk_emit_kernel(Walk a)
+{
+    emit_sweep<CommitWalk, false>(a, blockIdx.x, 0, Multi{});
+}
+
+/* ------------------------------------------------------- the record lister
+ * zscrc_device_records, active and finalised images: the three launches above
+ * (or the one-lane loop) as instances of RecordList. */
+__global__ __launch_bounds__(WG) void records_table_kernel(Walk a) { table_sweep<RecordList>(a, blockIdx.x); }
+
+__global__ __launch_bounds__(64) void records_serial_kernel(Walk a)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0)
+        serial_walk<RecordList>(a, HDR, 0, U64_MAX);
+}
+
+__global__ __launch_bounds__(WG) void records_chain_kernel(Walk a) { chain_walk<RecordList>(a); }
+
+__global__ __launch_bounds__(WG) void records_emit_kernel(Walk a)
+{
+    emit_sweep<RecordList, false>(a, blockIdx.x, 0, Multi{});
+}
+
+/* Packed images: the records in pointer-section order.  There is no chain --
+ * pointer i is parsed on its own -- but the host lister stops at the first
+ * pointer whose record does not parse, so the smallest failing index is found
+ * first (an integer min) and only the records before it are put out; record i
+ * is output entry i.
+ *
+ *   records_packed_locate_kernel  one lane: the two spans (packed_spans) and
+ *                                 the pointer count; the result words
+ *   records_packed_find_kernel    one pointer per thread, grid-stride: the
+ *                                 smallest index whose record does not parse
+ *   records_packed_emit_kernel    one pointer per thread, grid-stride, below
+ *                                 that index: stores and folds; res[0], res[1]
+ */
+struct Packed {
+    const uint8_t *img;
+    uint64_t size;
+    uint64_t *recs;
+    uint64_t cap;
+    uint64_t *res;
+    uint64_t *sc; /* scratch: PK_WORDS words */
+};
+/* PK_FAIL: the first pointer that does not parse, the count where all do */
+enum { PK_POFF = 0, PK_COUNT = 1, PK_FAIL = 2, PK_WORDS = 8 };
+constexpr unsigned PACKED_GRID_MAX = 2048;
+
+__global__ __launch_bounds__(64) void records_packed_locate_kernel(Packed a)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0)
+        return;
+    uint64_t so[2], sl[2], poff = 0, count = 0;
+    int rc = zsrec::packed_spans(zsrec::Direct{a.img}, a.size, so, sl);
+    if (rc == ZSCRC_OK) {
+        poff = so[1];
+        if (!zsrec::pointer_count(a.img, poff, sl[1], &count)) {
+            rc = ZSCRC_ZS_TRUNCATED;
+            count = 0;
+        }
+    }
+    a.sc[PK_POFF] = poff;
+    a.sc[PK_COUNT] = count;
+    a.sc[PK_FAIL] = count;
+    /* as the host returns it: no record listed where the sections are not
+     * found; the emit launch writes [0] and [1] where there are pointers */
+    a.res[0] = (uint64_t)(int64_t)rc;
+    a.res[1] = 0;
+    a.res[2] = poff;
+    for (int i = 3; i < ZSCRC_RECORDS_RES_WORDS; ++i)
+        a.res[i] = 0;
+    a.res[8] = U64_MAX;
+}
+
+__global__ __launch_bounds__(WG) void records_packed_find_kernel(Packed a)
+{
+    const uint64_t poff = a.sc[PK_POFF], count = a.sc[PK_COUNT];
+    const uint64_t stride = (uint64_t)gridDim.x * WG;
+    uint64_t fail = U64_MAX;
+    /* ascending: a thread's first failure is its smallest */
+    for (uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x; i < count && fail == U64_MAX; i += stride) {
+        zscrc_zs_record r;
+        uint64_t next;
+        if (!zsrec::record_at(a.img, a.size, zsrec::pointer_at(a.img, poff, i), r, &next))
+            fail = i;
+    }
+    if (fail != U64_MAX)
+        atomicMin(reinterpret_cast<unsigned long long *>(a.sc + PK_FAIL), (unsigned long long)fail);
+}
+
+__global__ __launch_bounds__(WG) void records_packed_emit_kernel(Packed a)
+{
+    __shared__ uint64_t s_fold[RecordList::FOLD];
+    const uint64_t poff = a.sc[PK_POFF], count = a.sc[PK_COUNT], n = a.sc[PK_FAIL];
+    const uint64_t stride = (uint64_t)gridDim.x * WG;
+    if (threadIdx.x == 0)
+        RecordList::fold_init(s_fold);
+    __syncthreads();
+    RecordList::Acc acc;
+    for (uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x; i < n; i += stride) {
+        zscrc_zs_record r;
+        uint64_t next;
+        /* parses: i is below the first index that does not */
+        if (!zsrec::record_at(a.img, a.size, zsrec::pointer_at(a.img, poff, i), r, &next))
+            continue;
+        if (i < a.cap)
+            RecordList::store_rec(a.recs, i, r);
+        RecordList::fold_rec(r, acc);
+    }
+    RecordList::fold_lds(s_fold, acc);
+    __syncthreads();
+    if (threadIdx.x != 0)
+        return;
+    RecordList::fold_words(a.res + 3, s_fold[0], s_fold[1], s_fold[2], s_fold[3], s_fold[4]);
+    if (blockIdx.x == 0 && count) {
+        a.res[0] = n > a.cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : n < count ? (uint64_t)ZSCRC_ZS_TRUNCATED : 0;
+        a.res[1] = n;
+    }
+}
 
 /* ------------------------------------------------- many images of one arena
  * zscrc_device_walk_multi: the same walk over k images of one device buffer
@@ -689,7 +979,7 @@ __global__ __launch_bounds__(WG) void walk_multi_table_kernel(MWalk a)
     const uint32_t blk = blockIdx.x - a.im[j].blk0;
     if (threadIdx.x == 0)
         w.entry[blk].slot = NONE;
-    table_sweep(w, blk);
+    table_sweep<CommitWalk>(w, blk);
 }
 
 __global__ __launch_bounds__(WG) void walk_multi_chain_kernel(MWalk a)
@@ -708,11 +998,11 @@ __global__ __launch_bounds__(WG) void walk_multi_chain_kernel(MWalk a)
         return;
     }
     uint64_t n, end, unaligned;
-    int rc = chain_hops(w, n, end, unaligned);
+    int rc = chain_hops<CommitWalk>(w, n, end, unaligned);
     a.tail_n[j] = n;
     if (unaligned != U64_MAX) { /* the spans' positions are not known yet: count */
         end = unaligned;
-        rc = serial_loop(w, end, [&n](uint64_t, uint64_t) { ++n; });
+        rc = serial_loop<CommitWalk>(w, end, [&n](uint64_t, const Step &) { ++n; });
     }
     row[0] = (uint64_t)rc;
     row[1] = n;
@@ -762,7 +1052,7 @@ __global__ __launch_bounds__(WG) void walk_multi_emit_kernel(MWalk a)
     if (blockIdx.x < a.nblocks) {
         const uint32_t j = image_of(a, blockIdx.x);
         const Walk w = view_of(a, j);
-        emit_sweep<true>(w, blockIdx.x - a.im[j].blk0, w.res[6], Multi{a.im[j].off, a.img, j, a.tot});
+        emit_sweep<CommitWalk, true>(w, blockIdx.x - a.im[j].blk0, w.res[6], Multi{a.im[j].off, a.img, j, a.tot});
     }
     const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
     if (j >= a.k || a.rows[j * ROW + 5] == U64_MAX)
@@ -770,8 +1060,8 @@ __global__ __launch_bounds__(WG) void walk_multi_emit_kernel(MWalk a)
     const Walk w = view_of(a, (uint32_t)j);
     const Multi m{a.im[j].off, a.img, (uint32_t)j, a.tot};
     uint64_t off = w.res[5], n = w.res[6] + a.tail_n[j], mx = 0, mn = U64_MAX;
-    (void)serial_loop(w, off, [&](uint64_t at, uint64_t span) {
-        put_span<true>(w, m, n++, at - span, span, mx, mn);
+    (void)serial_loop<CommitWalk>(w, off, [&](uint64_t at, const Step &s) {
+        put_span<true>(w, m, n++, at - s.span, s.span, mx, mn);
     });
     if (mn != U64_MAX) {
         fold_lengths(w.res + 3, mx, mn);
@@ -882,15 +1172,56 @@ int scratch_done(Scratch &sc, hipStream_t s, int rc)
     return rc;
 }
 
-int launch(const Walk &w, unsigned flags, hipStream_t s)
+/* records: the record lister's instances instead of the commit walk's. */
+int launch(const Walk &w, unsigned flags, hipStream_t s, bool records)
 {
+    const dim3 blocks((unsigned)w.nblocks);
     if (serial_only(w, flags)) {
-        hipLaunchKernelGGL(walk_serial_kernel, dim3(1), dim3(64), 0, s, w);
+        hipLaunchKernelGGL(records ? records_serial_kernel : walk_serial_kernel, dim3(1), dim3(64), 0, s, w);
     } else {
-        hipLaunchKernelGGL(walk_table_kernel, dim3((unsigned)w.nblocks), dim3(WG), 0, s, w);
-        hipLaunchKernelGGL(walk_chain_kernel, dim3(1), dim3(WG), 0, s, w);
-        hipLaunchKernelGGL(walk_emit_kernel, dim3((unsigned)w.nblocks), dim3(WG), 0, s, w);
+        hipLaunchKernelGGL(records ? records_table_kernel : walk_table_kernel, blocks, dim3(WG), 0, s, w);
+        hipLaunchKernelGGL(records ? records_chain_kernel : walk_chain_kernel, dim3(1), dim3(WG), 0, s, w);
+        hipLaunchKernelGGL(records ? records_emit_kernel : walk_emit_kernel, blocks, dim3(WG), 0, s, w);
     }
+    return hipGetLastError() == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+}
+
+/* The walk of one image (w: geometry, image, output and result pointers set)
+ * with the caller's scratch or, scratch == NULL, the library's. */
+int walk_single(Walk &w, void *scratch, unsigned flags, hipStream_t s, bool records)
+{
+    auto place = [&w](void *p) {
+        w.entry = static_cast<Entry *>(p);
+        w.J = reinterpret_cast<uint32_t *>(w.entry + w.nblocks);
+        w.C = w.J + w.ns;
+    };
+    if (serial_only(w, flags)) /* touches no scratch */
+        return launch(w, flags, s, records);
+    if (scratch) {
+        place(scratch);
+        return launch(w, flags, s, records);
+    }
+    Scratch *sc = device_scratch();
+    if (!sc)
+        return ZSCRC_ENODEV;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    const int arc = scratch_acquire(*sc, scratch_bytes(w), s);
+    if (arc)
+        return arc;
+    place(sc->p);
+    return scratch_done(*sc, s, launch(w, flags, s, records));
+}
+
+int launch_packed(const Packed &a, unsigned flags, hipStream_t s)
+{
+    /* the pointer count is on the device only: a grid for the most the image
+     * can hold (one pointer per 8 bytes), capped; the kernels stride */
+    uint64_t g = a.size / 8 / WG + 1;
+    if (g > PACKED_GRID_MAX || (flags & ZSCRC_WALK_SERIAL))
+        g = (flags & ZSCRC_WALK_SERIAL) ? 1 : PACKED_GRID_MAX;
+    hipLaunchKernelGGL(records_packed_locate_kernel, dim3(1), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(records_packed_find_kernel, dim3((unsigned)g), dim3(WG), 0, s, a);
+    hipLaunchKernelGGL(records_packed_emit_kernel, dim3((unsigned)g), dim3(WG), 0, s, a);
     return hipGetLastError() == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
 }
 
@@ -1014,27 +1345,51 @@ int zscrc_device_walk(const void *d_image, uint64_t image_size, uint64_t *d_span
     w.len = d_span_len;
     w.cap = cap;
     w.res = d_res;
+    return walk_single(w, scratch, flags, static_cast<hipStream_t>(stream), false);
+}
+
+size_t zscrc_device_records_scratch_bytes(uint64_t image_size, int kind, const zscrc_walk_opts *opts)
+{
+    Walk w{};
+    if ((kind != ZSCRC_ZS_ACTIVE && kind != ZSCRC_ZS_FINALISED && kind != ZSCRC_ZS_PACKED) ||
+        !geometry(image_size, opts, &w))
+        return 0;
+    return kind == ZSCRC_ZS_PACKED ? PK_WORDS * sizeof(uint64_t) : scratch_bytes(w);
+}
+
+int zscrc_device_records(const void *d_image, uint64_t image_size, int kind, struct zscrc_zs_record *d_recs,
+                         size_t cap, uint64_t *d_res, void *scratch, const zscrc_walk_opts *opts, unsigned flags,
+                         void *stream)
+{
+    Walk w{};
+    const bool packed = kind == ZSCRC_ZS_PACKED;
+    if (!d_image || !d_res || (cap && !d_recs) || (flags & ~ZSCRC_WALK_SERIAL) ||
+        (kind != ZSCRC_ZS_ACTIVE && kind != ZSCRC_ZS_FINALISED && !packed) ||
+        image_size < (packed ? HDR + 16 : HDR) || !geometry(image_size, opts, &w) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 15))
+        return ZSCRC_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    auto place = [&w](void *p) {
-        w.entry = static_cast<Entry *>(p);
-        w.J = reinterpret_cast<uint32_t *>(w.entry + w.nblocks);
-        w.C = w.J + w.ns;
-    };
-    if (serial_only(w, flags)) /* touches no scratch */
-        return launch(w, flags, s);
-    if (scratch) {
-        place(scratch);
-        return launch(w, flags, s);
+    if (!packed) {
+        w.img = static_cast<const uint8_t *>(d_image);
+        w.off = reinterpret_cast<uint64_t *>(d_recs); /* four words an entry (RecordList) */
+        w.len = nullptr;
+        w.cap = cap;
+        w.res = d_res;
+        return walk_single(w, scratch, flags, s, true);
     }
+    Packed a{static_cast<const uint8_t *>(d_image), image_size, reinterpret_cast<uint64_t *>(d_recs), cap, d_res,
+             static_cast<uint64_t *>(scratch)};
+    if (scratch)
+        return launch_packed(a, flags, s);
     Scratch *sc = device_scratch();
     if (!sc)
         return ZSCRC_ENODEV;
     std::lock_guard<std::mutex> lk(sc->mu);
-    const int arc = scratch_acquire(*sc, scratch_bytes(w), s);
+    const int arc = scratch_acquire(*sc, PK_WORDS * sizeof(uint64_t), s);
     if (arc)
         return arc;
-    place(sc->p);
-    return scratch_done(*sc, s, launch(w, flags, s));
+    a.sc = static_cast<uint64_t *>(sc->p);
+    return scratch_done(*sc, s, launch_packed(a, flags, s));
 }
 
 size_t zscrc_device_walk_multi_scratch_bytes(const zscrc_walk_image *images, size_t k, const zscrc_walk_opts *opts)

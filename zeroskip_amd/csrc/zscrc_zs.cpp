@@ -30,6 +30,7 @@
 
 #include "../../include/zscrc.h"
 #include "zscrc_internal.h"
+#include "zscrc_records.h"
 
 extern "C" int zscrc_internal_verify_commits(const void *d_image, uint64_t image_size, const uint64_t *d_off,
                                              const uint64_t *d_len, const uint32_t *d_seed, uint32_t *d_crc,
@@ -80,60 +81,10 @@ struct DeviceImage {
     }
 };
 
-/* Length of the commit record at off and its span; false if not a commit. */
-template <class Image>
-bool commit_at(const Image &im, uint64_t size, uint64_t off, uint64_t *span_len, uint64_t *rec_len)
-{
-    if (off + 8 > size)
-        return false;
-    const uint64_t w = im.word(off);
-    const unsigned t = (unsigned)(w >> 56);
-    if (t == T_COMMIT || t == T_FINAL) {
-        *span_len = (w >> 32) & 0xFFFFFF;
-        *rec_len = 8;
-    } else if (t == T_LONG_COMMIT || t == T_LONG_FINAL) {
-        if (off + 24 > size)
-            return false;
-        *span_len = im.word(off + 8);
-        *rec_len = 24;
-    } else {
-        return false;
-    }
-    return *span_len <= off;
-}
-
-/* zscrc_zs_packed_spans for an image in host or device memory. */
-template <class Image>
-int packed_spans(const Image &im, uint64_t size, uint64_t span_off[2], uint64_t span_len[2])
-{
-    if (size < HDR + 16)
-        return ZSCRC_EINVAL;
-    /* final commit at the end: short FINAL, or LONG_FINAL whose 2ND_HALF word
-     * ends the file (get_offset_to_pointers, zeroskip-packed.c:70-131) */
-    uint64_t foff = size - 8;
-    if ((im.word(foff) >> 56) == T_2ND)
-        foff = size - 24;
-    uint64_t sl, rl;
-    if (!commit_at(im, size, foff, &sl, &rl) || rl != size - foff)
-        return ZSCRC_ZS_TRUNCATED;
-    const unsigned ft = (unsigned)(im.word(foff) >> 56);
-    if (ft != T_FINAL && ft != T_LONG_FINAL)
-        return ZSCRC_ZS_TRUNCATED;
-    span_off[1] = foff - sl;
-    span_len[1] = sl;
-    /* the records-region commit ends where the pointer section starts */
-    const uint64_t pstart = foff - sl;
-    if (pstart < HDR + 8)
-        return ZSCRC_ZS_TRUNCATED;
-    uint64_t roff = pstart - 8;
-    if ((im.word(roff) >> 56) == T_2ND && pstart >= HDR + 24)
-        roff = pstart - 24;
-    if (!commit_at(im, size, roff, &sl, &rl) || roff + rl != pstart)
-        return ZSCRC_ZS_TRUNCATED;
-    span_off[0] = roff - sl;
-    span_len[0] = sl;
-    return ZSCRC_OK;
-}
+/* commit_at and packed_spans over either reader: zscrc_records.h (the device
+ * record lister reads a packed file's words through them in a kernel). */
+using zsrec::commit_at;
+using zsrec::packed_spans;
 
 /* The commits' statuses of a device-resident image into the report. */
 int verify_spans(const void *d_image, uint64_t size, const uint64_t *d_off, const uint64_t *d_len, size_t n,

@@ -137,6 +137,48 @@ def verify_device_image(d_image: torch.Tensor, kind: int = ACTIVE) -> dict:
     return rep.as_dict()
 
 
+RECORDS_RES_WORDS = 12  # ZSCRC_RECORDS_RES_WORDS
+DELETED = -1  # val_off of a delete record as int64 (ZSCRC_ZS_DELETED, UINT64_MAX)
+
+
+def records_scratch_bytes(size: int, kind: int = ACTIVE, block_bytes: int = 0, tile_bytes: int = 0) -> int:
+    """zscrc_device_records_scratch_bytes; 0 = bad options or kind."""
+    return lib().zscrc_device_records_scratch_bytes(size, kind, ctypes.byref(WalkOpts(block_bytes, tile_bytes)))
+
+
+def device_records(d_image: torch.Tensor, kind: int = ACTIVE, cap: int | None = None, block_bytes: int = 0,
+                   tile_bytes: int = 0, serial: bool = False, out: tuple | None = None,
+                   scratch: torch.Tensor | None = None):
+    """The key / value and delete records of a device-resident image, listed
+    on the GPU (zscrc_device_records), asynchronous on the current stream:
+    (recs, res) int64 device tensors.  recs is [cap, 4] -- key_off, key_len,
+    val_off (DELETED for a delete record), val_len -- of which the first
+    min(res[1], cap) rows are written; the default cap is size // 24 + 1, the
+    most an image can hold (no record is shorter than 24 bytes).  res =
+    [result code, records, end offset (packed: the pointer section's offset),
+    deletes, sum of key lengths, sum of value lengths, longest key, longest
+    value, offset a one-lane loop took over at or -1, 0, 0, 0].  Equal to
+    repack.records() of the same bytes.  out: preallocated (recs, res) to
+    write into; scratch: a 16-byte aligned uint8 tensor of
+    records_scratch_bytes() bytes (default: the library's own, stream-ordered)."""
+    size = d_image.numel() * d_image.element_size()
+    dev = d_image.device
+    if cap is None:
+        cap = size // 24 + 1
+    if out is None:
+        out = (torch.empty((max(cap, 1), 4), dtype=torch.int64, device=dev),
+               torch.empty(RECORDS_RES_WORDS, dtype=torch.int64, device=dev))
+    recs, res = out
+    assert recs.numel() >= 4 * cap and res.numel() >= RECORDS_RES_WORDS
+    opts = WalkOpts(block_bytes, tile_bytes)
+    with torch.cuda.device(dev):
+        check(lib().zscrc_device_records(
+            d_image.data_ptr(), size, kind, recs.data_ptr() if recs.numel() else None, cap, res.data_ptr(),
+            None if scratch is None else scratch.data_ptr(), ctypes.byref(opts), WALK_SERIAL if serial else 0,
+            torch.cuda.current_stream(dev).cuda_stream), "zscrc_device_records")
+    return recs, res
+
+
 class WalkImage(ctypes.Structure):
     """zscrc_walk_image (include/zscrc.h): bytes [off, off + size) of an arena."""
     _fields_ = [("off", ctypes.c_uint64), ("size", ctypes.c_uint64)]
