@@ -64,6 +64,30 @@ __device__ __forceinline__ void gstore32(const void *p, uint32_t v)
 {
     *(gw32p)reinterpret_cast<uintptr_t>(p) = v;
 }
+/* The four words of a loaded 16-byte block into w[0..3]. */
+__device__ __forceinline__ void put4(const u32x4 v, uint32_t *w)
+{
+    w[0] = v.x;
+    w[1] = v.y;
+    w[2] = v.z;
+    w[3] = v.w;
+}
+
+/* One 16-byte load at address a into w[0..3]; NT: non-temporal. */
+template <bool NT = false>
+__device__ __forceinline__ void ld16(uintptr_t a, uint32_t *w)
+{
+    put4(NT ? __builtin_nontemporal_load((g4p)a) : *(g4p)a, w);
+}
+
+/* Wavefront fence over a per-wave LDS scratch: the lanes' writes before it
+ * are seen by every lane's reads after it. */
+__device__ __forceinline__ void wave_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 #ifndef ZS_DIAG_BLOCK_STORE
 #define ZS_DIAG_BLOCK_STORE 0 /* 1, 2: A/B diagnostic builds of the writer (emit; 2: + nt run loads) */
 #endif
@@ -378,26 +402,16 @@ __device__ __forceinline__ void issue(const Cursor &c, int j, uintptr_t dummy, u
             q[i] = p + 16 * i;
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const u32x4 v = *(g4p)q[i];
-        w[4 * i + 0] = v.x;
-        w[4 * i + 1] = v.y;
-        w[4 * i + 2] = v.z;
-        w[4 * i + 3] = v.w;
-    }
+    for (int i = 0; i < 4; ++i)
+        ld16(q[i], w + 4 * i);
 }
 
 /* Four plain 16-byte loads of the piece at p (interior steps). */
 __device__ __forceinline__ void issue_plain(uintptr_t p, uint32_t (&w)[16])
 {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const u32x4 v = *(g4p)(p + 16 * i);
-        w[4 * i + 0] = v.x;
-        w[4 * i + 1] = v.y;
-        w[4 * i + 2] = v.z;
-        w[4 * i + 3] = v.w;
-    }
+    for (int i = 0; i < 4; ++i)
+        ld16(p + 16 * i, w + 4 * i);
 }
 
 /* Read the big-endian 64-bit word at a (8-aligned in a zeroskip file). */
@@ -920,22 +934,13 @@ __device__ __forceinline__ void xissue(uintptr_t step, bool ok, uint32_t voff, u
         for (int i = 0; i < 4; ++i) {
             uintptr_t q = sb + voff + 1024u * (uint32_t)i;
             q = q < lo ? lo : q;
-            const u32x4 v = __builtin_nontemporal_load((g4p)q);
-            w[4 * i + 0] = v.x;
-            w[4 * i + 1] = v.y;
-            w[4 * i + 2] = v.z;
-            w[4 * i + 3] = v.w;
+            ld16<true>(q, w + 4 * i);
         }
         return;
     }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const u32x4 v = __builtin_nontemporal_load((g4p)(sb + (voff + 1024u * (uint32_t)i)));
-        w[4 * i + 0] = v.x;
-        w[4 * i + 1] = v.y;
-        w[4 * i + 2] = v.z;
-        w[4 * i + 3] = v.w;
-    }
+    for (int i = 0; i < 4; ++i)
+        ld16<true>(sb + (voff + 1024u * (uint32_t)i), w + 4 * i);
 }
 
 /* block i of lane (g, c) <-> block g of lane (i, c): v_permlane32_swap then
@@ -1571,6 +1576,96 @@ extern "C" int zs_set_classify_times(uint64_t *p)
  * past the last record (a partial last group) load a dummy line and store
  * nothing.
  */
+/* What the qteam kernels' prologues share: the lane's place in its wave, and
+ * the geometry every record of the batch has -- span = E - A, S steps of
+ * 1 KiB ending at E, the grid starting pad bytes before A. */
+struct QGeom {
+    int lane, t, j;       /* lane (g, 4t+h): record t of the group, piece j = 4g+h of the team's step */
+    uint32_t c_lo, c_hi;  /* the lane's table replica (m4) */
+    uint64_t wave, nwaves;
+    uintptr_t base, dummy, lo;
+    uint64_t n, ngroups, gstride, span, pad;
+    uint32_t S, tail, R0;
+    uint32_t voff; /* lane offset of its 16-byte block in instruction 0 */
+};
+
+__device__ __forceinline__ QGeom qgeom(const XDesc &d, const uint32_t *gtab)
+{
+    QGeom q;
+    const int lane = threadIdx.x & 63, g = lane >> 4, t = (lane >> 2) & 3, h = lane & 3;
+    q.lane = lane;
+    q.t = t;
+    q.j = 4 * g + h;
+    q.c_lo = (uint32_t)(lane & 31) << 2;
+    q.c_hi = q.c_lo | 0x10000u;
+    q.wave = uni64((uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6));
+    q.nwaves = (uint64_t)gridDim.x * WAVES;
+    q.n = d.n;
+    q.ngroups = (d.n + 3) / 4;
+    q.base = reinterpret_cast<uintptr_t>(d.base);
+    const uint64_t len = d.fixed_len;
+    const uint64_t ph = q.base & 3;
+    q.span = ((ph + len) & ~uint64_t(3)) - ph;
+    q.S = (uint32_t)((q.span + 1023) / 1024);
+    q.pad = (uint64_t)q.S * 1024 - q.span;
+    q.tail = (uint32_t)(len - q.span);
+    q.R0 = d.seed ^ d.xor_io;
+    q.dummy = reinterpret_cast<uintptr_t>(gtab);
+    q.lo = q.base & ~uintptr_t(3);
+    q.gstride = 4 * d.stride;
+    q.voff = (uint32_t)((uint64_t)t * d.stride) + 64u * (uint32_t)h + 16u * (uint32_t)g;
+    return q;
+}
+
+/* issue the four loads of step s of group k (wave-uniform k, s; k = ngroups:
+ * none, a dummy line) */
+__device__ __forceinline__ void qissue(const QGeom &q, uint64_t k, uint32_t s, uint32_t (&w)[16])
+{
+    const bool any = k < q.ngroups;
+    const uintptr_t sb = uni64(any ? q.base + k * q.gstride + (uint64_t)s * 1024 - q.pad : q.dummy);
+    if (any && (sb < q.lo || 4 * k + 4 > q.n)) {
+        /* the buffer's first group with front padding, or a partial last
+         * group: per-lane clamped / dummy addresses */
+        const bool live = 4 * k + (uint64_t)q.t < q.n;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            uintptr_t a = sb + q.voff + 256u * (uint32_t)i;
+            a = !live ? q.dummy : a < q.lo ? q.lo : a;
+            ld16<true>(a, w + 4 * i);
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        ld16<true>(sb + (any ? q.voff + 256u * (uint32_t)i : 0u), w + 4 * i);
+}
+
+/* The last piece of a team's record (or part), then the team fold: lane
+ * j's register sits (15-j)*64 bytes before E (pieces j and j - 2^k are lanes
+ * 2^k apart for k < 2, rows apart above); the team's register in lane
+ * j == 15. */
+template <int B3>
+__device__ __forceinline__ uint32_t qteam_end(const char *L, const QGeom &q, uint32_t acc, const uint32_t (&w)[16])
+{
+    acc = piece<false, B3>(L, acc, w, q.c_lo, q.c_hi);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t sh = op4(L, OFF_Z + 4096u * k, acc);
+        const uint32_t other = __shfl(sh, q.lane - (k < 2 ? (1 << k) : (16 << (k - 2))));
+        acc ^= (q.j & (1 << k)) ? other : 0u;
+    }
+    return acc;
+}
+
+/* The record's 0-3 bytes past its last 4-aligned address (lane j == 15). */
+__device__ __forceinline__ uint32_t qteam_tail(const char *L, const QGeom &q, uintptr_t A, uint32_t acc)
+{
+    const g8p e = (g8p)(A + q.span);
+    for (uint32_t i = 0; i < q.tail; ++i)
+        acc = byte_step(L, acc, e[i], q.c_hi);
+    return acc;
+}
+
 template <int B3>
 __global__ __launch_bounds__(WG) void qteam_kernel(XDesc d, const uint32_t *__restrict__ gtab)
 {
@@ -1582,57 +1677,10 @@ __global__ __launch_bounds__(WG) void qteam_kernel(XDesc d, const uint32_t *__re
     fill_lds<16>(L, gtab);
     __syncthreads();
     const uint64_t t_fill = __builtin_amdgcn_s_memrealtime();
-    const int lane = threadIdx.x & 63, g = lane >> 4, t = (lane >> 2) & 3, h = lane & 3;
-    const int j = 4 * g + h; /* piece of the team's step */
-    const uint32_t c_lo = (uint32_t)(lane & 31) << 2;
-    const uint32_t c_hi = c_lo | 0x10000u;
-    const uint64_t wave = uni64((uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6));
-    const uint64_t nwaves = (uint64_t)gridDim.x * WAVES;
-    /* record geometry, the same for every record: span = E - A, S steps of
-     * 1 KiB ending at E, the grid starting pad bytes before A */
-    const uintptr_t base = reinterpret_cast<uintptr_t>(d.base);
-    const uint64_t len = d.fixed_len;
-    const uint64_t ph = base & 3;
-    const uint64_t span = ((ph + len) & ~uint64_t(3)) - ph;
-    const uint32_t S = (uint32_t)((span + 1023) / 1024);
-    const uint64_t pad = (uint64_t)S * 1024 - span;
-    const uint32_t tail = (uint32_t)(len - span);
-    const uint32_t R0 = d.seed ^ d.xor_io;
-    const uintptr_t dummy = reinterpret_cast<uintptr_t>(gtab);
-    const uintptr_t lo = base & ~uintptr_t(3);
-    const uint64_t gstride = 4 * d.stride;
-    /* lane offset of its 16-byte block in instruction 0 */
-    const uint32_t voff = (uint32_t)((uint64_t)t * d.stride) + 64u * (uint32_t)h + 16u * (uint32_t)g;
-
-    /* issue the four loads of step s of group k (wave-uniform k, s) */
-    auto issue = [&](uint64_t k, uint32_t s, uint32_t (&w)[16]) {
-        const bool any = k < ngroups;
-        const uintptr_t sb = uni64(any ? base + k * gstride + (uint64_t)s * 1024 - pad : dummy);
-        if (any && (sb < lo || 4 * k + 4 > d.n)) {
-            /* the buffer's first group with front padding, or a partial last
-             * group: per-lane clamped / dummy addresses */
-            const bool live = 4 * k + (uint64_t)t < d.n;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                uintptr_t q = sb + voff + 256u * (uint32_t)i;
-                q = !live ? dummy : q < lo ? lo : q;
-                const u32x4 v = __builtin_nontemporal_load((g4p)q);
-                w[4 * i + 0] = v.x;
-                w[4 * i + 1] = v.y;
-                w[4 * i + 2] = v.z;
-                w[4 * i + 3] = v.w;
-            }
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const u32x4 v = __builtin_nontemporal_load((g4p)(sb + (any ? voff + 256u * (uint32_t)i : 0u)));
-            w[4 * i + 0] = v.x;
-            w[4 * i + 1] = v.y;
-            w[4 * i + 2] = v.z;
-            w[4 * i + 3] = v.w;
-        }
-    };
+    const QGeom G = qgeom(d, gtab);
+    const int lane = G.lane;
+    const uint32_t c_lo = G.c_lo, c_hi = G.c_hi, S = G.S;
+    const uint64_t wave = G.wave, nwaves = G.nwaves;
 
     uint64_t kL = wave; /* load cursor: one step ahead of the hashing */
     uint32_t sL = 0;
@@ -1640,7 +1688,7 @@ __global__ __launch_bounds__(WG) void qteam_kernel(XDesc d, const uint32_t *__re
     uint32_t sH = 0;
     uint32_t acc = 0;
     uint32_t b0[16], b1[16];
-    issue(kL, sL, b0);
+    qissue(G, kL, sL, b0);
     auto advance_load = [&]() {
         if (++sL == S) {
             sL = 0;
@@ -1649,34 +1697,23 @@ __global__ __launch_bounds__(WG) void qteam_kernel(XDesc d, const uint32_t *__re
     };
     auto hash = [&](uint32_t (&w)[16]) {
         xpose16(w);
-        const uint64_t rec = 4 * kH + (uint64_t)t;
-        const uintptr_t A = base + rec * d.stride;
+        const uint64_t rec = 4 * kH + (uint64_t)G.t;
+        const uintptr_t A = G.base + rec * d.stride;
         /* the record start lies in step 0, or its first 4 bytes reach step 1 */
-        if (sH == 0 || (sH == 1 && pad > 1020)) {
+        if (sH == 0 || (sH == 1 && G.pad > 1020)) {
             XItem it;
             it.A = A;
-            it.R0 = R0;
-            fix_piece(it, A - pad + (uint64_t)sH * 1024 + 64 * (uintptr_t)j, lo, w);
+            it.R0 = G.R0;
+            fix_piece(it, A - G.pad + (uint64_t)sH * 1024 + 64 * (uintptr_t)G.j, G.lo, w);
         }
         if (sH + 1 < S) {
             acc = piece<true, B3>(L, acc, w, c_lo, c_hi);
             ++sH;
             return;
         }
-        acc = piece<false, B3>(L, acc, w, c_lo, c_hi);
-        /* lane j's register sits (15-j)*64 bytes before E: fold the team
-         * (pieces j and j - 2^k are lanes 2^k apart for k < 2, rows apart
-         * above) */
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t sh = op4(L, OFF_Z + 4096u * k, acc);
-            const uint32_t other = __shfl(sh, lane - (k < 2 ? (1 << k) : (16 << (k - 2))));
-            acc ^= (j & (1 << k)) ? other : 0u;
-        }
-        if (j == 15 && rec < d.n) {
-            const g8p e = (g8p)(A + span);
-            for (uint32_t i = 0; i < tail; ++i)
-                acc = byte_step(L, acc, e[i], c_hi);
+        acc = qteam_end<B3>(L, G, acc, w);
+        if (G.j == 15 && rec < d.n) {
+            acc = qteam_tail(L, G, A, acc);
             d.out[rec] = acc ^ d.xor_io;
         }
         acc = 0;
@@ -1685,12 +1722,12 @@ __global__ __launch_bounds__(WG) void qteam_kernel(XDesc d, const uint32_t *__re
     };
     while (kH < ngroups) {
         advance_load();
-        issue(kL, sL, b1);
+        qissue(G, kL, sL, b1);
         hash(b0);
         if (kH >= ngroups)
             break;
         advance_load();
-        issue(kL, sL, b0);
+        qissue(G, kL, sL, b0);
         hash(b1);
     }
     uint64_t *wt = zs_wave_times; /* diagnostic (zscrc_diag_wave_times) */
@@ -1739,24 +1776,10 @@ __global__ __launch_bounds__(WG) void qteam_dyn_kernel(XDesc d, QDyn q, const ui
     fill_lds<16>(L, gtab);
     __syncthreads();
     const uint64_t t_fill = __builtin_amdgcn_s_memrealtime();
-    const int lane = threadIdx.x & 63, g = lane >> 4, t = (lane >> 2) & 3, h = lane & 3;
-    const int j = 4 * g + h; /* piece of the team's step */
-    const uint32_t c_lo = (uint32_t)(lane & 31) << 2;
-    const uint32_t c_hi = c_lo | 0x10000u;
-    const uint64_t wave = uni64((uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6));
-    const uint64_t nwaves = (uint64_t)gridDim.x * WAVES;
-    const uintptr_t base = reinterpret_cast<uintptr_t>(d.base);
-    const uint64_t len = d.fixed_len;
-    const uint64_t ph = base & 3;
-    const uint64_t span = ((ph + len) & ~uint64_t(3)) - ph;
-    const uint32_t S = (uint32_t)((span + 1023) / 1024);
-    const uint64_t pad = (uint64_t)S * 1024 - span;
-    const uint32_t tail = (uint32_t)(len - span);
-    const uint32_t R0 = d.seed ^ d.xor_io;
-    const uintptr_t dummy = reinterpret_cast<uintptr_t>(gtab);
-    const uintptr_t lo = base & ~uintptr_t(3);
-    const uint64_t gstride = 4 * d.stride;
-    const uint32_t voff = (uint32_t)((uint64_t)t * d.stride) + 64u * (uint32_t)h + 16u * (uint32_t)g;
+    const QGeom G = qgeom(d, gtab);
+    const int lane = G.lane;
+    const uint32_t c_lo = G.c_lo, c_hi = G.c_hi, S = G.S;
+    const uint64_t wave = G.wave, nwaves = G.nwaves;
     /* part p = steps [part_lo(p), part_hi(p)) */
     auto part_hi = [&](uint32_t p) { return S - (np - 1 - p) * P; };
     auto part_lo = [&](uint32_t p) { return p ? S - (np - p) * P : 0u; };
@@ -1769,67 +1792,31 @@ __global__ __launch_bounds__(WG) void qteam_dyn_kernel(XDesc d, QDyn q, const ui
         return u;
     };
 
-    /* a unit as (group k, part p); k = ngroups: none left */
-    auto issue = [&](uint64_t k, uint32_t s, uint32_t (&w)[16]) {
-        const bool any = k < ngroups;
-        const uintptr_t sb = uni64(any ? base + k * gstride + (uint64_t)s * 1024 - pad : dummy);
-        if (any && (sb < lo || 4 * k + 4 > d.n)) {
-            const bool live = 4 * k + (uint64_t)t < d.n;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                uintptr_t a = sb + voff + 256u * (uint32_t)i;
-                a = !live ? dummy : a < lo ? lo : a;
-                const u32x4 v = __builtin_nontemporal_load((g4p)a);
-                w[4 * i + 0] = v.x;
-                w[4 * i + 1] = v.y;
-                w[4 * i + 2] = v.z;
-                w[4 * i + 3] = v.w;
-            }
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const u32x4 v = __builtin_nontemporal_load((g4p)(sb + (any ? voff + 256u * (uint32_t)i : 0u)));
-            w[4 * i + 0] = v.x;
-            w[4 * i + 1] = v.y;
-            w[4 * i + 2] = v.z;
-            w[4 * i + 3] = v.w;
-        }
-    };
-
     uint32_t acc = 0;
     /* in-LDS part registers (q.lds_fold): local record 4 gi + t of the
      * workgroup's gi-th group, np registers each */
     uint32_t *lparts = reinterpret_cast<uint32_t *>(L + OFF_Z + 4 * 4096 + 16);
+    /* a unit as (group k, part p); k = ngroups: none left */
     auto hash = [&](uint32_t (&w)[16], uint64_t k, uint32_t p, uint32_t s, uint32_t gi) {
         xpose16(w);
-        const uint64_t rec = 4 * k + (uint64_t)t;
-        const uintptr_t A = base + rec * d.stride;
-        if (s == 0 || (s == 1 && pad > 1020)) {
+        const uint64_t rec = 4 * k + (uint64_t)G.t;
+        const uintptr_t A = G.base + rec * d.stride;
+        if (s == 0 || (s == 1 && G.pad > 1020)) {
             XItem it;
             it.A = A;
-            it.R0 = R0;
-            fix_piece(it, A - pad + (uint64_t)s * 1024 + 64 * (uintptr_t)j, lo, w);
+            it.R0 = G.R0;
+            fix_piece(it, A - G.pad + (uint64_t)s * 1024 + 64 * (uintptr_t)G.j, G.lo, w);
         }
         if (s + 1 < part_hi(p)) {
             acc = piece<true, B3>(L, acc, w, c_lo, c_hi);
             return false;
         }
-        acc = piece<false, B3>(L, acc, w, c_lo, c_hi);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const uint32_t sh = op4(L, OFF_Z + 4096u * kk, acc);
-            const uint32_t other = __shfl(sh, lane - (kk < 2 ? (1 << kk) : (16 << (kk - 2))));
-            acc ^= (j & (1 << kk)) ? other : 0u;
-        }
-        if (j == 15 && rec < d.n) {
-            if (p + 1 == np) {
-                const g8p e = (g8p)(A + span);
-                for (uint32_t i = 0; i < tail; ++i)
-                    acc = byte_step(L, acc, e[i], c_hi);
-            }
+        acc = qteam_end<B3>(L, G, acc, w);
+        if (G.j == 15 && rec < d.n) {
+            if (p + 1 == np)
+                acc = qteam_tail(L, G, A, acc);
             if (q.lds_fold)
-                lparts[(4 * gi + (uint32_t)t) * np + p] = acc;
+                lparts[(4 * gi + (uint32_t)G.t) * np + p] = acc;
             else
                 q.part_out[rec * np + p] = acc;
         }
@@ -1867,14 +1854,14 @@ __global__ __launch_bounds__(WG) void qteam_dyn_kernel(XDesc d, QDyn q, const ui
     uint64_t k0 = lk, k1;
     uint32_t p0 = lp, p1, s0 = ls, s1, g0 = lg, g1;
     uint32_t units = 0;
-    issue(lk, ls, b0);
+    qissue(G, lk, ls, b0);
     while (k0 < ngroups) {
         advance_load();
         k1 = lk;
         p1 = lp;
         s1 = ls;
         g1 = lg;
-        issue(k1, s1, b1);
+        qissue(G, k1, s1, b1);
         units += hash(b0, k0, p0, s0, g0) ? 1u : 0u;
         if (k1 >= ngroups)
             break;
@@ -1883,7 +1870,7 @@ __global__ __launch_bounds__(WG) void qteam_dyn_kernel(XDesc d, QDyn q, const ui
         p0 = lp;
         s0 = ls;
         g0 = lg;
-        issue(k0, s0, b0);
+        qissue(G, k0, s0, b0);
         units += hash(b1, k1, p1, s1, g1) ? 1u : 0u;
     }
     uint64_t *wt = zs_wave_times; /* diagnostic (zscrc_diag_wave_times) */
@@ -2143,14 +2130,9 @@ __global__ __launch_bounds__(WG) void short_kernel(BatchDesc d, const uint32_t *
                 for (int p = 0; p < NPB; ++p) {
                     const uint32_t o = base + p < np ? (uint32_t)(V0 + 64 * (base + p) - W) : OOB;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const u32x4 v = __builtin_bit_cast(
-                            u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + 16 * q, 0, 0));
-                        buf[p][4 * q + 0] = v.x;
-                        buf[p][4 * q + 1] = v.y;
-                        buf[p][4 * q + 2] = v.z;
-                        buf[p][4 * q + 3] = v.w;
-                    }
+                    for (int q = 0; q < 4; ++q)
+                        put4(__builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + 16 * q, 0, 0)),
+                             buf[p] + 4 * q);
                 }
                 if (have)
                     put(pend, pend_r);
@@ -2356,14 +2338,15 @@ struct M64Pos {
     uint64_t b, k;
 };
 
+/* Issue the 4 K loads of chunk k of batch b (wave-uniform; !ok: no chunk, a
+ * dummy line). */
 template <int K>
-__device__ __forceinline__ void m64_issue(const MultiBatch &m, uint64_t n, const M64Pos &p, uint32_t voff,
-                                          uintptr_t dummy, uint32_t (&w)[16 * K])
+__device__ __forceinline__ void m64_issue(const MultiBatch &m, uint64_t n, uint64_t b, uint64_t k, bool ok,
+                                          uint32_t voff, uintptr_t dummy, uint32_t (&w)[16 * K])
 {
     constexpr uint64_t CHUNK = 4096ull * K;
-    const bool ok = p.b < m.nb;
-    const uintptr_t base = ok ? reinterpret_cast<uintptr_t>(m.base[ok ? p.b : 0]) : dummy;
-    const uintptr_t sb = uni64(base + (ok ? p.k * CHUNK : 0));
+    const uintptr_t base = ok ? reinterpret_cast<uintptr_t>(m.base[ok ? b : 0]) : dummy;
+    const uintptr_t sb = uni64(base + (ok ? k * CHUNK : 0));
     /* loads past the batch's last record read its last 16 bytes: a scalar
      * bound on the 32-bit lane offset, no branch (a branchy clamp made the
      * compiler wait for the next chunk's loads before hashing this one) */
@@ -2372,12 +2355,35 @@ __device__ __forceinline__ void m64_issue(const MultiBatch &m, uint64_t n, const
 #pragma unroll
     for (int i = 0; i < 4 * K; ++i) {
         const uint32_t o = voff + 1024u * (uint32_t)i;
-        const u32x4 v = __builtin_nontemporal_load((g4p)(sb + (o < lim ? o : lim)));
-        w[4 * i + 0] = v.x;
-        w[4 * i + 1] = v.y;
-        w[4 * i + 2] = v.z;
-        w[4 * i + 3] = v.w;
+        ld16<true>(sb + (o < lim ? o : lim), w + 4 * i);
     }
+}
+
+/* A loaded chunk's K records per lane: the row transpose; r[q] = the
+ * register of record 64 q + lane of the chunk before its word 1. */
+template <int K>
+__device__ __forceinline__ void m64_begin(uint32_t (&w)[16 * K], uint32_t R0, uint32_t (&r)[K])
+{
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        xpose16(reinterpret_cast<uint32_t (&)[16]>(w[16 * q]));
+        r[q] = w[16 * q] ^ R0; /* register before word k, XOR word k */
+    }
+}
+
+/* The K records as K interleaved chains; r[q] = raw register at the end. */
+template <int K>
+__device__ __forceinline__ void m64_chains(const char *L, const uint32_t (&w)[16 * K], uint32_t c_lo, uint32_t c_hi,
+                                           uint32_t (&r)[K])
+{
+#pragma unroll
+    for (int k = 1; k < 16; ++k)
+#pragma unroll
+        for (int q = 0; q < K; ++q)
+            r[q] = m4x<ZS_MULTI_B3>(L, r[q], w[16 * q + k], c_lo, c_hi);
+#pragma unroll
+    for (int q = 0; q < K; ++q)
+        r[q] = m4(L, r[q], c_lo, c_hi);
 }
 
 /* K = records per lane per chunk (independent chains); K = 3 measured slower
@@ -2483,14 +2489,10 @@ __global__ __launch_bounds__(WG) void multi64_kernel(BatchDesc d, MultiBatch m, 
         snext = lane == 0 ? atomicAdd(&lslot, 1u) : 0u;
     };
     pl = ph;
-    m64_issue<K>(m, n, pl, voff, dummy, b0);
+    m64_issue<K>(m, n, pl.b, pl.k, pl.b < m.nb, voff, dummy, b0);
     auto hash = [&](uint32_t (&w)[16 * K], const M64Pos &p) {
         uint32_t r[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-            xpose16(reinterpret_cast<uint32_t (&)[16]>(w[16 * q]));
-            r[q] = w[16 * q] ^ R0; /* register before word k, XOR word k */
-        }
+        m64_begin<K>(w, R0, r);
         if (d.opt & (1u << 20)) { /* diagnostic: the load + store shape alone (wrong results) */
 #pragma unroll
             for (int k = 1; k < 16; ++k)
@@ -2498,14 +2500,7 @@ __global__ __launch_bounds__(WG) void multi64_kernel(BatchDesc d, MultiBatch m, 
                 for (int q = 0; q < K; ++q)
                     r[q] ^= w[16 * q + k];
         } else {
-#pragma unroll
-            for (int k = 1; k < 16; ++k)
-#pragma unroll
-                for (int q = 0; q < K; ++q)
-                    r[q] = m4x<ZS_MULTI_B3>(L, r[q], w[16 * q + k], c_lo, c_hi);
-#pragma unroll
-            for (int q = 0; q < K; ++q)
-                r[q] = m4(L, r[q], c_lo, c_hi);
+            m64_chains<K>(L, w, c_lo, c_hi, r);
         }
         uint32_t *out = m.out[p.b];
         uint64_t r0 = p.k * RPC + (uint64_t)lane;
@@ -2531,13 +2526,13 @@ __global__ __launch_bounds__(WG) void multi64_kernel(BatchDesc d, MultiBatch m, 
         M64Pos pn;
         while (ph.b < m.nb) {
             deal_advance(pn);
-            m64_issue<K>(m, n, pn, voff, dummy, b1);
+            m64_issue<K>(m, n, pn.b, pn.k, pn.b < m.nb, voff, dummy, b1);
             hash(b0, ph);
             ph = pn;
             if (ph.b >= m.nb)
                 break;
             deal_advance(pn);
-            m64_issue<K>(m, n, pn, voff, dummy, b0);
+            m64_issue<K>(m, n, pn.b, pn.k, pn.b < m.nb, voff, dummy, b0);
             hash(b1, ph);
             ph = pn;
         }
@@ -2545,13 +2540,13 @@ __global__ __launch_bounds__(WG) void multi64_kernel(BatchDesc d, MultiBatch m, 
     }
     while (ph.b < m.nb) {
         advance(pl);
-        m64_issue<K>(m, n, pl, voff, dummy, b1);
+        m64_issue<K>(m, n, pl.b, pl.k, pl.b < m.nb, voff, dummy, b1);
         hash(b0, ph);
         advance(ph);
         if (ph.b >= m.nb)
             break;
         advance(pl);
-        m64_issue<K>(m, n, pl, voff, dummy, b0);
+        m64_issue<K>(m, n, pl.b, pl.k, pl.b < m.nb, voff, dummy, b0);
         hash(b1, ph);
         advance(ph);
     }
@@ -2571,26 +2566,6 @@ __global__ __launch_bounds__(WG) void multi64_kernel(BatchDesc d, MultiBatch m, 
  * alone.
  */
 constexpr int M64_GROUP = 4;
-
-template <int K>
-__device__ __forceinline__ void m64d_issue(const MultiBatch &m, uint64_t n, uint64_t b, uint64_t k, bool ok,
-                                           uint32_t voff, uintptr_t dummy, uint32_t (&w)[16 * K])
-{
-    constexpr uint64_t CHUNK = 4096ull * K;
-    const uintptr_t base = ok ? reinterpret_cast<uintptr_t>(m.base[b]) : dummy;
-    const uintptr_t sb = uni64(base + (ok ? k * CHUNK : 0));
-    const uint64_t room = ok ? base + n * 64 - 16 - sb : 0;
-    const uint32_t lim = rfl_u32((uint32_t)(room < 0xffffffffull ? room : 0xffffffffull));
-#pragma unroll
-    for (int i = 0; i < 4 * K; ++i) {
-        const uint32_t o = voff + 1024u * (uint32_t)i;
-        const u32x4 v = __builtin_nontemporal_load((g4p)(sb + (o < lim ? o : lim)));
-        w[4 * i + 0] = v.x;
-        w[4 * i + 1] = v.y;
-        w[4 * i + 2] = v.z;
-        w[4 * i + 3] = v.w;
-    }
-}
 
 __global__ __launch_bounds__(WG) void multi64d_kernel(BatchDesc d, MultiBatch m, const uint32_t *__restrict__ gtab)
 {
@@ -2640,38 +2615,25 @@ __global__ __launch_bounds__(WG) void multi64d_kernel(BatchDesc d, MultiBatch m,
     ph.q = wave - ph.b * gpb;
     ph.j = 0;
     pl = ph;
-    m64d_issue<K>(m, n, pl.b, pl.q * M64_GROUP + pl.j, chunk_ok(pl), voff, dummy, b0);
+    m64_issue<K>(m, n, pl.b, pl.q * M64_GROUP + pl.j, chunk_ok(pl), voff, dummy, b0);
     auto hash = [&](uint32_t (&w)[16 * K], const Pos &p) {
         uint32_t r[K];
-#pragma unroll
-        for (int q = 0; q < K; ++q) {
-            xpose16(reinterpret_cast<uint32_t (&)[16]>(w[16 * q]));
-            r[q] = w[16 * q] ^ R0;
-        }
-        if (nohash) {
+        m64_begin<K>(w, R0, r);
+        if (nohash) { /* diagnostic: the load + store shape alone (wrong results) */
 #pragma unroll
             for (int k = 1; k < 16; ++k)
 #pragma unroll
                 for (int q = 0; q < K; ++q)
                     r[q] ^= w[16 * q + k];
         } else {
-#pragma unroll
-            for (int k = 1; k < 16; ++k)
-#pragma unroll
-                for (int q = 0; q < K; ++q)
-                    r[q] = m4x<ZS_MULTI_B3>(L, r[q], w[16 * q + k], c_lo, c_hi);
-#pragma unroll
-            for (int q = 0; q < K; ++q)
-                r[q] = m4(L, r[q], c_lo, c_hi);
+            m64_chains<K>(L, w, c_lo, c_hi, r);
         }
 #pragma unroll
         for (int q = 0; q < K; ++q)
             S[RPC * p.j + 64 * q + lane] = r[q] ^ d.xor_io;
         if (p.j == M64_GROUP - 1 || p.q * M64_GROUP + p.j + 1 >= cpb) {
             /* the group's results: one contiguous block, written after its reads */
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_fence();
             uint32_t *out = m.out[p.b];
             const uint64_t r0 = p.q * M64_GROUP * RPC;
 #pragma unroll
@@ -2685,14 +2647,14 @@ __global__ __launch_bounds__(WG) void multi64d_kernel(BatchDesc d, MultiBatch m,
     };
     while (ph.b < m.nb) {
         advance(pl);
-        m64d_issue<K>(m, n, pl.b, pl.q * M64_GROUP + pl.j, chunk_ok(pl), voff, dummy, b1);
+        m64_issue<K>(m, n, pl.b, pl.q * M64_GROUP + pl.j, chunk_ok(pl), voff, dummy, b1);
         if (chunk_ok(ph))
             hash(b0, ph);
         advance(ph);
         if (ph.b >= m.nb)
             break;
         advance(pl);
-        m64d_issue<K>(m, n, pl.b, pl.q * M64_GROUP + pl.j, chunk_ok(pl), voff, dummy, b0);
+        m64_issue<K>(m, n, pl.b, pl.q * M64_GROUP + pl.j, chunk_ok(pl), voff, dummy, b0);
         if (chunk_ok(ph))
             hash(b1, ph);
         advance(ph);
@@ -2884,11 +2846,7 @@ __device__ __forceinline__ void burst_issue_x(const BRec &b, uintptr_t dummy, ui
 #pragma unroll
         for (int p = 0; p < NB; ++p) {
             const uintptr_t q = bt ? V + 64 * (uint32_t)(p < (int)np_t ? p : np_t - 1) + 16 * g : dummy + 16 * g;
-            const u32x4 v = *(g4p)q;
-            w[p][4 * t + 0] = v.x;
-            w[p][4 * t + 1] = v.y;
-            w[p][4 * t + 2] = v.z;
-            w[p][4 * t + 3] = v.w;
+            ld16(q, w[p] + 4 * t);
         }
     }
 }
@@ -2979,90 +2937,8 @@ __device__ __forceinline__ void run_issue(const BRec &b, uint32_t (&w)[NB][16], 
 #pragma unroll
     for (int p = 0; p < NB; ++p)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const g4p a = (g4p)(V + 4096u * p + 1024u * t + voff);
-            const u32x4 v = NT ? __builtin_nontemporal_load(a) : *a;
-            w[p][4 * t + 0] = v.x;
-            w[p][4 * t + 1] = v.y;
-            w[p][4 * t + 2] = v.z;
-            w[p][4 * t + 3] = v.w;
-        }
-}
-
-/* Pieces P0 .. P0+NP-1 of a run round as NP interleaved chains; their
- * shifted registers to the scratch. */
-template <int P0, int NP, int NB>
-__device__ __forceinline__ void run_chains(const BRec &b, uint32_t (&w)[NB][16], const char *L, uint32_t *S,
-                                           int lane, uint32_t c_lo, uint32_t c_hi, uint32_t opt)
-{
-    uint32_t y[NP];
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const int p = P0 + q;
-        const uint32_t P = 64u * p + (uint32_t)lane;
-        const uint32_t r = (P * 205u) >> 10; /* P / 5 for P < 1024 */
-        const uint32_t r0 = __shfl(b.it.R0, (int)r);
-        if (P == 5u * r) { /* piece 0 of record r */
-            if (r) {       /* the previous record's commit word */
-                S[320 + 2 * (r - 1)] = w[p][0];
-                S[321 + 2 * (r - 1)] = w[p][1];
-            }
-            w[p][0] = 0;
-            w[p][1] = 0;
-            w[p][2] ^= r0;
-        }
-        y[q] = w[p][0];
-    }
-    if (!(opt & 4096)) {
-#pragma unroll
-        for (int k = 1; k < 16; ++k)
-#pragma unroll
-            for (int q = 0; q < NP; ++q)
-                y[q] = m4x<ZS_COMMIT_B3>(L, y[q], w[P0 + q][k], c_lo, c_hi);
-    } else {
-#pragma unroll
-        for (int k = 1; k < 16; ++k)
-#pragma unroll
-            for (int q = 0; q < NP; ++q)
-                y[q] ^= w[P0 + q][k];
-    }
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const uint32_t P = 64u * (P0 + q) + (uint32_t)lane;
-        const uint32_t m = P - 5u * ((P * 205u) >> 10);
-        const uint32_t raw = m4(L, y[q], c_lo, c_hi);
-        const uint32_t tb = OFF_U + (m == 3 ? 0u : m == 2 ? 4096u : m == 1 ? OFF_Z192 : OFF_Z2);
-        const uint32_t sh = op4(L, tb, raw);
-        S[P] = m == 4 ? raw : sh;
-    }
-}
-
-/* After xpose_burst: lane L holds pieces 64p + L of the round. */
-template <int NB>
-__device__ __forceinline__ void run_hash(const BatchDesc &d, BRec &b, uint32_t (&w)[NB][16], const char *L,
-                                         uint32_t *S, int lane, uint32_t c_lo, uint32_t c_hi)
-{
-    static_assert(NB == 5, "run rounds are five-piece rounds");
-    /* the lane's piece / record indices are recomputed every round: hoisted
-     * out of the loop they held ~15 VGPRs across it and the kernel spilled */
-    asm volatile("" : "+v"(lane));
-    run_chains<0, 3>(b, w, L, S, lane, c_lo, c_hi, d.opt);
-    run_chains<3, 2>(b, w, L, S, lane, c_lo, c_hi, d.opt);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint32_t *q = S + 5 * lane;
-    const uint32_t reg = xor3(q[0], q[1], q[2]) ^ q[3] ^ q[4];
-    if (b.cnext) {
-        b.it.c0 = S[320 + 2 * lane];
-        b.it.c1 = S[321 + 2 * lane];
-    }
-    if (d.opt & 8192) { /* diagnostic: no per-record trailer / stores */
-        if (reg == 0x9E3779B9u)
-            gstore32(d.out, reg);
-        return;
-    }
-    emit(d, b.it, reg, L, c_lo, c_hi);
+        for (int t = 0; t < 4; ++t)
+            ld16<NT>(V + 4096u * p + 1024u * t + voff, w[p] + 4 * t);
 }
 
 /* The run-only commit_kernel's scratch (12 waves per CU leave no room for
@@ -3071,10 +2947,15 @@ __device__ __forceinline__ void run_hash(const BatchDesc &d, BRec &b, uint32_t (
  * linearity), then 128 words of commit words. */
 constexpr uint32_t RUN_WORDS_RO = 64 + 128;
 
-template <int P0, int NP, int NB>
-__device__ __forceinline__ void run_chains_ro(const BRec &b, uint32_t (&w)[NB][16], const char *L, uint32_t *S,
-                                              int lane, uint32_t c_lo, uint32_t c_hi, uint32_t opt)
+/* Pieces P0 .. P0+NP-1 of a run round as NP interleaved chains; their
+ * shifted registers to the scratch.  RO (the RUN_WORDS_RO scratch): commit
+ * words from word 64, not 320, and piece P's register XOR-ed into its
+ * record's accumulator S[P / 5] instead of stored to S[P]. */
+template <bool RO, int P0, int NP, int NB>
+__device__ __forceinline__ void run_chains(const BRec &b, uint32_t (&w)[NB][16], const char *L, uint32_t *S,
+                                           int lane, uint32_t c_lo, uint32_t c_hi, uint32_t opt)
 {
+    constexpr uint32_t CW = RO ? 64 : 320; /* the commit words' place in the scratch */
     uint32_t y[NP];
 #pragma unroll
     for (int q = 0; q < NP; ++q) {
@@ -3084,8 +2965,8 @@ __device__ __forceinline__ void run_chains_ro(const BRec &b, uint32_t (&w)[NB][1
         const uint32_t r0 = __shfl(b.it.R0, (int)r);
         if (P == 5u * r) { /* piece 0 of record r */
             if (r) {       /* the previous record's commit word */
-                S[64 + 2 * (r - 1)] = w[p][0];
-                S[65 + 2 * (r - 1)] = w[p][1];
+                S[CW + 2 * (r - 1)] = w[p][0];
+                S[CW + 1 + 2 * (r - 1)] = w[p][1];
             }
             w[p][0] = 0;
             w[p][1] = 0;
@@ -3114,8 +2995,44 @@ __device__ __forceinline__ void run_chains_ro(const BRec &b, uint32_t (&w)[NB][1
         const uint32_t raw = m4(L, y[q], c_lo, c_hi);
         const uint32_t tb = OFF_U + (m == 3 ? 0u : m == 2 ? 4096u : m == 1 ? OFF_Z192 : OFF_Z2);
         const uint32_t sh = op4(L, tb, raw);
-        atomicXor(&S[r], m == 4 ? raw : sh);
+        if (RO)
+            atomicXor(&S[r], m == 4 ? raw : sh);
+        else
+            S[P] = m == 4 ? raw : sh;
     }
+}
+
+/* The end of a run round, after the fence behind its chains: lane's record
+ * has register reg; C = the scratch's commit words. */
+__device__ __forceinline__ void run_finish(const BatchDesc &d, BRec &b, uint32_t reg, const uint32_t *C,
+                                           const char *L, int lane, uint32_t c_lo, uint32_t c_hi)
+{
+    if (b.cnext) {
+        b.it.c0 = C[2 * lane];
+        b.it.c1 = C[2 * lane + 1];
+    }
+    if (d.opt & 8192) { /* diagnostic: no per-record trailer / stores */
+        if (reg == 0x9E3779B9u)
+            gstore32(d.out, reg);
+        return;
+    }
+    emit(d, b.it, reg, L, c_lo, c_hi);
+}
+
+/* After xpose_burst: lane L holds pieces 64p + L of the round. */
+template <int NB>
+__device__ __forceinline__ void run_hash(const BatchDesc &d, BRec &b, uint32_t (&w)[NB][16], const char *L,
+                                         uint32_t *S, int lane, uint32_t c_lo, uint32_t c_hi)
+{
+    static_assert(NB == 5, "run rounds are five-piece rounds");
+    /* the lane's piece / record indices are recomputed every round: hoisted
+     * out of the loop they held ~15 VGPRs across it and the kernel spilled */
+    asm volatile("" : "+v"(lane));
+    run_chains<false, 0, 3>(b, w, L, S, lane, c_lo, c_hi, d.opt);
+    run_chains<false, 3, 2>(b, w, L, S, lane, c_lo, c_hi, d.opt);
+    wave_fence();
+    const uint32_t *q = S + 5 * lane;
+    run_finish(d, b, xor3(q[0], q[1], q[2]) ^ q[3] ^ q[4], S + 320, L, lane, c_lo, c_hi);
 }
 
 /* run_hash for the run-only commit_kernel (RUN_WORDS_RO scratch). */
@@ -3124,25 +3041,11 @@ __device__ __forceinline__ void run_hash_ro(const BatchDesc &d, BRec &b, uint32_
 {
     asm volatile("" : "+v"(lane));
     S[lane] = 0; /* the wave's record accumulators (its LDS ops stay in order) */
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    run_chains_ro<0, 3>(b, w, L, S, lane, c_lo, c_hi, d.opt);
-    run_chains_ro<3, 2>(b, w, L, S, lane, c_lo, c_hi, d.opt);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint32_t reg = S[lane];
-    if (b.cnext) {
-        b.it.c0 = S[64 + 2 * lane];
-        b.it.c1 = S[65 + 2 * lane];
-    }
-    if (d.opt & 8192) { /* diagnostic: no per-record trailer / stores */
-        if (reg == 0x9E3779B9u)
-            gstore32(d.out, reg);
-        return;
-    }
-    emit(d, b.it, reg, L, c_lo, c_hi);
+    wave_fence();
+    run_chains<true, 0, 3>(b, w, L, S, lane, c_lo, c_hi, d.opt);
+    run_chains<true, 3, 2>(b, w, L, S, lane, c_lo, c_hi, d.opt);
+    wave_fence();
+    run_finish(d, b, S[lane], S + 64, L, lane, c_lo, c_hi);
 }
 
 /* Piece p (< 2) of a grid whose record starts d0 bytes in (0..63): the
@@ -3240,11 +3143,7 @@ __device__ __forceinline__ void quad_piece(const QuadRound &Q, uint32_t p, uintp
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const uintptr_t q = p < Q.np[t] ? Q.V[t] + 64u * p + 16u * g : dummy + 16u * g;
-        const u32x4 v = *(g4p)q;
-        w[0][4 * t + 0] = v.x;
-        w[0][4 * t + 1] = v.y;
-        w[0][4 * t + 2] = v.z;
-        w[0][4 * t + 3] = v.w;
+        ld16(q, w[0] + 4 * t);
     }
 }
 
@@ -5264,10 +5163,12 @@ extern "C" int zs_launch_team(int g, int fixed, int depth, const zs::BatchDesc *
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-extern "C" int zs_launch_xteam(int depth, const zs::BatchDesc *bd, const uint32_t *gtab, int grid,
-                               hipStream_t stream)
+/* The XDesc of a fixed-stride batch (last_len: the last record's own length
+ * where the batch sets one). */
+static zs::XDesc xdesc_of(const zs::BatchDesc *bd)
 {
     zs::XDesc x;
+    memset(&x, 0, sizeof x);
     x.base = bd->base;
     x.out = bd->out;
     x.n = bd->n;
@@ -5276,6 +5177,29 @@ extern "C" int zs_launch_xteam(int depth, const zs::BatchDesc *bd, const uint32_
     x.last_len = bd->last_len == ~0ull ? bd->fixed_len : bd->last_len;
     x.seed = bd->fixed_seed;
     x.xor_io = bd->xor_io;
+    return x;
+}
+
+/* xteam_kernel's arguments for the modes that do not read them: no spans
+ * (only k is read), no parts. */
+static zs::XMulti no_spans()
+{
+    zs::XMulti m;
+    m.k = 0;
+    return m;
+}
+
+static zs::XParts no_parts()
+{
+    zs::XParts p;
+    memset(&p, 0, sizeof p);
+    return p;
+}
+
+extern "C" int zs_launch_xteam(int depth, const zs::BatchDesc *bd, const uint32_t *gtab, int grid,
+                               hipStream_t stream)
+{
+    const zs::XDesc x = xdesc_of(bd);
     const zs::XDesc *d = &x;
     /* equal-length records, stride % 4 == 0 (host checks); tuning bits 4 / 8
      * pick the XOR3 groupings for A/B runs */
@@ -5286,10 +5210,8 @@ extern "C" int zs_launch_xteam(int depth, const zs::BatchDesc *bd, const uint32_
     else if (depth == 16)
         hipLaunchKernelGGL(zs::qteam_kernel<ZS_QTEAM_B3>, dim3(grid), dim3(zs::WG), 0, stream, *d, gtab);
     else {
-        zs::XMulti none;
-        none.k = 0;
-        zs::XParts np;
-        memset(&np, 0, sizeof np);
+        const zs::XMulti none = no_spans();
+        const zs::XParts np = no_parts();
         if (bd->opt & zs::OPT_XDEAL) /* a span's segments, dealt per workgroup */
             hipLaunchKernelGGL((zs::xteam_kernel<0, true>), dim3(grid), dim3(zs::WG), 0, stream, *d, none, np, gtab);
         else
@@ -5305,10 +5227,8 @@ extern "C" int zs_launch_xparts(const zs::BatchDesc *bd, const uint32_t *gtab, i
     zs::XDesc x;
     memset(&x, 0, sizeof x);
     x.base = bd->base;
-    zs::XMulti none;
-    none.k = 0;
-    zs::XParts p;
-    memset(&p, 0, sizeof p);
+    const zs::XMulti none = no_spans();
+    zs::XParts p = no_parts();
     p.base = bd->base;
     p.desc = bd->desc;
     p.class_count = bd->class_count;
@@ -5338,8 +5258,7 @@ extern "C" int zs_launch_nbv(const zs::XParts *p, const uint32_t *gtab, int grid
     zs::XDesc x;
     memset(&x, 0, sizeof x);
     x.base = p->base;
-    zs::XMulti none;
-    none.k = 0;
+    const zs::XMulti none = no_spans();
     hipLaunchKernelGGL(zs::xteam_kernel<3>, dim3(grid), dim3(zs::WG), 0, stream, x, none, *p, gtab);
     if (hipGetLastError() != hipSuccess)
         return -3;
@@ -5400,16 +5319,7 @@ extern "C" int zs_launch_burst(int fixed, int xp, int nb, const zs::BatchDesc *d
 extern "C" int zs_launch_qdyn(const zs::BatchDesc *bd, const zs::QDyn *q, uint32_t K, uint32_t K_last,
                               const uint32_t *gtab, int grid, hipStream_t stream)
 {
-    zs::XDesc x;
-    memset(&x, 0, sizeof x);
-    x.base = bd->base;
-    x.out = bd->out;
-    x.n = bd->n;
-    x.stride = bd->stride;
-    x.fixed_len = bd->fixed_len;
-    x.last_len = bd->fixed_len;
-    x.seed = bd->fixed_seed;
-    x.xor_io = bd->xor_io;
+    const zs::XDesc x = xdesc_of(bd); /* (qteam_fits: no shorter last record) */
     hipLaunchKernelGGL(zs::qteam_dyn_kernel<ZS_QTEAM_B3>, dim3(grid), dim3(zs::WG), 0, stream, x, *q, gtab);
     if (hipGetLastError() != hipSuccess)
         return -3;
@@ -5535,8 +5445,7 @@ extern "C" int zs_launch_multi(const zs::BatchDesc *d, const zs::MultiBatch *m, 
 extern "C" int zs_launch_spans(const zs::XDesc *x, const zs::XMulti *m, const zs::SpanFolds *fs,
                                const uint32_t *gtab, int grid, int deal, hipStream_t stream)
 {
-    zs::XParts np;
-    memset(&np, 0, sizeof np);
+    const zs::XParts np = no_parts();
     if (deal)
         hipLaunchKernelGGL((zs::xteam_kernel<1, true>), dim3(grid), dim3(zs::WG), 0, stream, *x, *m, np, gtab);
     else
