@@ -616,6 +616,65 @@ int zscrc_device_records(const void *d_image, uint64_t image_size, int kind,
                          struct zscrc_zs_record *d_recs, size_t cap, uint64_t *d_res,
                          void *scratch, const zscrc_walk_opts *opts, unsigned flags, void *stream);
 
+/* The packed-file writer on the device: zscrc_pack_open / _add / _close
+ * (further down) for a record list and its bytes that live in device memory --
+ * d_out[0 .. file_bytes) receives exactly the bytes the host writer puts into
+ * its file for the same records, uuid and indices: the header with its CRC,
+ * key records (long above 65,535 bytes), value records (long above 16,777,215),
+ * the padding to 8 bytes, the records-region commit (long above 16,777,215
+ * bytes of region), the count and the big-endian pointers (pointer i = the file
+ * offset of record i) and the final commit; a delete whose key is longer than
+ * 65,535 bytes gets the host writer's bytes too (first word zero).  No byte of
+ * the source or the output crosses PCIe.
+ * Record i is d_recs[i], an entry such as zscrc_device_records writes: key_off
+ * / val_off are offsets into d_src (an arena of several images: the caller
+ * adds each image's offset), val_off == ZSCRC_ZS_DELETED a delete record
+ * (val_len ignored).  Records are written in the caller's order (the merge is
+ * the caller's, as for zscrc_pack_add); they may come in any order, repeat, and
+ * share or overlap source bytes.  Record headers are always generated from the
+ * lengths, never copied from the source.
+ * Launches in stream order (per-block lengths, one workgroup's scan and layout,
+ * record starts and pointers, the tiled copy, the library's variable-length
+ * batch over the two spans, one lane that seals commits and header); no
+ * workgroup waits for another.  tile_bytes: the output bytes of one work item
+ * of the copy, a power of two, 64 <= tile <= 64 KiB, 0 = the default (64 KiB).
+ * Limits: n <= 2^31 - 1, src_size <= 2^62. */
+typedef struct zscrc_pack_opts { uint64_t tile_bytes; } zscrc_pack_opts;  /* NULL = defaults */
+#define ZSCRC_PACK_RES_WORDS 8
+/* A host-computable upper bound on file_bytes from the lister's res[1], res[4],
+ * res[5]: 120 + 62 n + sum_key_len + sum_val_len; 0 if that wraps.  (Exact:
+ * 40 + R + c(R) + 8 (n + 1) + c(8 (n + 1)), R the records region, c(x) = 8 for
+ * x <= 16777215, else 24; an empty list gives 64 bytes.) */
+uint64_t zscrc_device_pack_bound(uint64_t n, uint64_t sum_key_len, uint64_t sum_val_len);
+/* Bytes of scratch zscrc_device_pack needs for n records: 8 a record, 8 per
+ * 1,024 records and a few words; a multiple of 16, monotone in n.  0 = a bad
+ * option or n above the limit. */
+size_t zscrc_device_pack_scratch_bytes(size_t n, const zscrc_pack_opts *opts);
+/* Asynchronous on `stream`: nothing is copied to the host, nothing waits.
+ * d_res (device, ZSCRC_PACK_RES_WORDS words):
+ *   [0] 0 = written; ZSCRC_ZS_OVERFLOW = the file needs more than out_cap
+ *       bytes; (uint64_t)(int64_t)ZSCRC_EINVAL = some record does not lie
+ *       inside [0, src_size) (checked against the bytes left, never with an
+ *       add that can wrap).  In both failure cases no byte of d_out is written.
+ *   [1] n, or on a bad record the smallest index of one
+ *   [2] file_bytes, exact (valid for 0 and OVERFLOW; UINT64_MAX if it does
+ *       not fit 64 bits)   [3] region_bytes
+ *   [4] region_crc  [5] pointers_crc  [6] commit_crc  [7] final_crc: the fields
+ *       of zscrc_pack_report (further down); 0 unless [0] == 0
+ * d_out == NULL with out_cap == 0 is the sizing call: OVERFLOW, [1..3] filled.
+ * scratch: 16-byte aligned device memory of zscrc_device_pack_scratch_bytes
+ * bytes, or NULL for the walk's per-device library scratch (zscrc_device_walk:
+ * stream-ordered between calls, kept until zscrc_release_cache).
+ * ZSCRC_EINVAL before any device call: d_res or uuid NULL; n > 0 with d_recs
+ * NULL; d_src NULL with src_size > 0; out_cap > 0 with d_out NULL; d_out or
+ * scratch not 16-byte aligned; [d_out, +out_cap) overlapping [d_src,
+ * +src_size); flags != 0; a bad option; n or src_size above its limit. */
+int zscrc_device_pack(const void *d_src, uint64_t src_size,
+                      const struct zscrc_zs_record *d_recs, size_t n,
+                      const uint8_t uuid[16], uint32_t startidx, uint32_t endidx,
+                      void *d_out, uint64_t out_cap, uint64_t *d_res, void *scratch,
+                      const zscrc_pack_opts *opts, unsigned flags, void *stream);
+
 /* `consistent` for one process / one GPU (zsdb_consistent,
  * src/zeroskip.c:1399-1407, and tool/cmd-consistent.c:23-49 are stubs in the
  * reference): every .zsdb / header / commit CRC of the DB directory,

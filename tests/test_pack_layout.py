@@ -1,0 +1,75 @@
+"""The device packer's layout arithmetic (zeroskip_amd/csrc/zscrc_pack_layout.h,
+the functions the kernels of zscrc_devpack.hip call) on the CPU: a stand-alone
+program (tests/c/pack_layout.cpp) rebuilds the packed file of each record list
+of tests/pack_cases.py word by word through them, at tile sizes 64, 128, 4096
+and 65536, and compares it with the format oracle's file.  The program is
+built with the address and undefined-behaviour sanitizers and runs as its own
+process; nothing is preloaded and nothing of it is loaded into python.  No GPU."""
+import os
+import struct
+import subprocess
+
+import pytest
+
+from tests import pack_cases as pc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "c", "pack_layout.cpp")
+
+
+@pytest.fixture(scope="module")
+def program(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("pack_layout") / "pack_layout")
+    base = [os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", SRC, "-o", exe]
+    r = subprocess.run(base[:1] + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] + base[1:],
+                       capture_output=True, text=True)
+    sanitized = r.returncode == 0
+    if not sanitized:
+        print("sanitizer build failed, building without:\n" + r.stderr[-2000:])
+        subprocess.run(base, check=True)
+    return exe, sanitized
+
+
+def _run(program, tmp_path, case, shift):
+    path = str(tmp_path / "case.bin")
+    want = case.want
+    with open(path, "wb") as fh:
+        fh.write(struct.pack("<6Q", len(case.src), len(case.recs), len(want), shift, case.startidx, case.endidx))
+        fh.write(case.uuid + case.src + case.recs.tobytes() + want)
+    r = subprocess.run([program[0], path], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (case.name, shift, r.stdout[-500:], r.stderr[-3000:])
+    assert r.stdout.startswith("ok %d records %d bytes" % (len(case.recs), len(want)))
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return pc.small_cases()
+
+
+def test_sanitizers_are_linked(program):
+    """The build with -fsanitize=address,undefined succeeded (without it the
+    cases below still compare every byte, but see no read outside the source)."""
+    assert program[1]
+
+
+def test_every_small_case(program, cases, tmp_path):
+    names = [c.name for c in cases]
+    assert len(set(names)) == len(names) >= 18
+    for case in cases:
+        _run(program, tmp_path, case, shift=0)
+
+
+@pytest.mark.parametrize("shift", range(1, 8))
+def test_source_address_residues(program, cases, tmp_path, shift):
+    """The alignment grid and the shared-bytes list from a source at every address mod 8."""
+    for case in cases:
+        if case.name in ("alignment_grid", "shared_bytes", "single_kv", "long_delete"):
+            _run(program, tmp_path, case, shift)
+
+
+def test_a_wrong_byte_is_seen(program, cases, tmp_path):
+    """The comparison has teeth: one byte of the expected file changed fails the run."""
+    case = next(c for c in cases if c.name == "single_kv")
+    bad = pc.Case("single_kv_wrong", case.src, case.recs, want=case.want[:64] + bytes([case.want[64] ^ 1]) + case.want[65:])
+    with pytest.raises(AssertionError):
+        _run(program, tmp_path, bad, 0)

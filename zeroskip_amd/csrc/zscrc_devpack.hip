@@ -1,0 +1,451 @@
+/*
+ * zscrc_devpack.hip -- the packed-file writer of zscrc_pack.cpp on the device:
+ * zscrc_device_pack writes the byte-exact packed file of a device-resident
+ * record list into device memory, CRCs included, with no image byte crossing
+ * PCIe ("The packer on the device").  The layout arithmetic is
+ * zscrc_pack_layout.h's, shared with the host.
+ *
+ * Launches, all in stream order, no workgroup waiting for another one:
+ *
+ *   pack_size_kernel    one workgroup per BLOCK_RECS records: every record
+ *                       checked against the source (the smallest bad index by
+ *                       an integer min) and the block's sum of serialised
+ *                       lengths
+ *   pack_scan_kernel    one workgroup: the block sums to their exclusive
+ *                       prefix, the layout (region, commits short or long,
+ *                       pointer section, file size), the result words [0..3],
+ *                       the two spans to checksum as device descriptors and
+ *                       the count that heads the pointer section
+ *   pack_prefix_kernel  one workgroup per block: each record's start in the
+ *                       region (8 bytes a record) and its big-endian pointer
+ *   pack_copy_kernel    the hot path: the file is cut into output tiles; a
+ *                       workgroup takes a run of consecutive tiles, finds the
+ *                       first record that reaches into it by binary search,
+ *                       keeps the starts of a tile's records in LDS, and every
+ *                       thread builds whole aligned 16-byte output words out
+ *                       of generated header words, padding and source bytes
+ *                       gathered from any alignment
+ *   (the library's variable-length batch over the two span descriptors)
+ *   pack_seal_kernel    one lane: the two commit records from the span CRCs,
+ *                       the header, the result words [4..7]
+ *
+ * The host never learns the region's size: grids are sized from the record
+ * count and the output's capacity, the kernels read the totals the scan left
+ * on the device.  A result code other than 0 makes every later kernel return
+ * at once, and the span descriptors empty.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <mutex>
+
+#include "../../include/zscrc.h"
+#include "zscrc_internal.h"
+#include "zscrc_pack_layout.h"
+
+namespace {
+
+using namespace zspack;
+
+constexpr int WG = 256;
+constexpr uint32_t PER = 4;                       /* records a thread of a block */
+constexpr uint32_t BLOCK_RECS = WG * PER;
+constexpr uint64_t N_MAX = (1ull << 31) - 1;      /* records of one call */
+constexpr uint64_t DEF_TILE = 65536, TILE_MIN = 64, TILE_MAX = 65536;
+/* starts of a tile's records in LDS: the most records that reach into a tile
+ * (24 bytes each at least), one more for the end, rounded up to whole rounds
+ * of WG loads */
+constexpr uint32_t LDS_STARTS = ((uint32_t)(TILE_MAX / 24) + 3 + WG - 1) / WG * WG + WG;
+/* what the 24 KiB of starts admit on a CU: every workgroup of the copy is
+ * resident, so the equal runs of tiles end together.  (An instance with 8 KiB
+ * of starts for tiles up to 16 KiB, eight workgroups a CU, was measured and
+ * was no faster there: DESIGN.md 2.6.) */
+constexpr unsigned COPY_WG_PER_CU = 6;
+
+/* scratch: SC_WORDS words, then nblocks + 1 block sums, then n + 1 starts */
+enum { SC_BAD = 0, SC_CODE = 1, SC_REGION = 2, SC_PTR_OFF = 3, SC_DOFF = 4, SC_DLEN = 6, SC_CRC = 8, SC_WORDS = 16 };
+
+struct Pack {
+    const uint8_t *src;
+    uint64_t src_size;
+    const zscrc_zs_record *recs;
+    uint64_t n;
+    uint8_t *out;
+    uint64_t out_cap;
+    uint64_t *res;
+    uint64_t *sc;     /* SC_WORDS words */
+    uint64_t *bsum;   /* nblocks + 1 */
+    uint64_t *start;  /* n + 1 */
+    uint64_t nblocks;
+    uint64_t tile;
+};
+
+__device__ inline uint64_t wave_sum_sat(uint64_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        v = sat_add(v, __shfl_down(v, d, 64));
+    return v;
+}
+
+/* Exclusive saturating prefix sum of one value a thread over the workgroup;
+ * total = the sum of all.  s: WG / 64 words of LDS, free again on return. */
+__device__ inline uint64_t wg_scan_sat(uint64_t *s, uint64_t mine, uint64_t &total)
+{
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t inc = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_up(inc, d, 64);
+        if (lane >= (unsigned)d)
+            inc = sat_add(inc, o);
+    }
+    if (lane == 63)
+        s[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+#pragma unroll
+    for (unsigned w = 0; w < WG / 64; ++w) {
+        if (w < wave)
+            before = sat_add(before, s[w]);
+        all = sat_add(all, s[w]);
+    }
+    __syncthreads();
+    total = all;
+    /* exclusive: what lies before this thread; saturated sums stay saturated */
+    const uint64_t upto = sat_add(before, inc);
+    return upto == U64_MAX ? U64_MAX : upto - mine;
+}
+
+/* The serialised length of record i, 0 past the list or for a bad record. */
+__device__ inline uint64_t len_of(const Pack &a, uint64_t i, bool *bad)
+{
+    *bad = false;
+    if (i >= a.n)
+        return 0;
+    const zscrc_zs_record r = a.recs[i];
+    if (!rec_ok(r, a.src_size)) {
+        *bad = true;
+        return 0;
+    }
+    return rec_len(r);
+}
+
+__global__ __launch_bounds__(WG) void pack_size_kernel(Pack a)
+{
+    __shared__ uint64_t s_part[WG / 64];
+    const uint64_t first = (uint64_t)blockIdx.x * BLOCK_RECS;
+    uint64_t sum = 0, bad_at = U64_MAX;
+#pragma unroll
+    for (uint32_t k = 0; k < PER; ++k) {
+        const uint64_t i = first + k * WG + threadIdx.x;
+        bool bad;
+        sum = sat_add(sum, len_of(a, i, &bad));
+        if (bad && i < bad_at)
+            bad_at = i;
+    }
+    if (bad_at != U64_MAX)
+        atomicMin(reinterpret_cast<unsigned long long *>(a.sc + SC_BAD), (unsigned long long)bad_at);
+    sum = wave_sum_sat(sum);
+    if ((threadIdx.x & 63) == 0)
+        s_part[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+        for (unsigned w = 0; w < WG / 64; ++w)
+            t = sat_add(t, s_part[w]);
+        a.bsum[blockIdx.x] = t;
+    }
+}
+
+__global__ __launch_bounds__(WG) void pack_scan_kernel(Pack a)
+{
+    __shared__ uint64_t s_scan[WG / 64];
+    const uint64_t chunk = (uint64_t)WG * PER;
+    uint64_t carry = 0;
+    for (uint64_t c = 0; c < a.nblocks; c += chunk) {
+        const uint64_t first = c + (uint64_t)threadIdx.x * PER;
+        uint64_t v[PER], mine = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            v[k] = first + k < a.nblocks ? a.bsum[first + k] : 0;
+            mine = sat_add(mine, v[k]);
+        }
+        uint64_t total;
+        uint64_t at = sat_add(carry, wg_scan_sat(s_scan, mine, total));
+#pragma unroll
+        for (uint32_t k = 0; k < PER; ++k) {
+            if (first + k < a.nblocks)
+                a.bsum[first + k] = at;
+            at = sat_add(at, v[k]);
+        }
+        carry = sat_add(carry, total);
+    }
+    if (threadIdx.x != 0)
+        return;
+    const uint64_t bad = a.n ? a.sc[SC_BAD] : U64_MAX;
+    const Layout l = layout(a.n, carry);
+    const uint64_t code = bad != U64_MAX ? (uint64_t)(int64_t)ZSCRC_EINVAL
+                                         : l.file_bytes > a.out_cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : 0;
+    a.res[0] = code;
+    a.res[1] = bad != U64_MAX ? bad : a.n;
+    a.res[2] = l.file_bytes;
+    a.res[3] = l.region;
+    for (int i = 4; i < ZSCRC_PACK_RES_WORDS; ++i)
+        a.res[i] = 0;
+    a.sc[SC_CODE] = code;
+    a.sc[SC_REGION] = l.region;
+    a.sc[SC_PTR_OFF] = l.ptr_off;
+    /* the spans the batch checksums: records region, pointer section */
+    a.sc[SC_DOFF] = code ? 0 : HDR;
+    a.sc[SC_DOFF + 1] = code ? 0 : l.ptr_off;
+    a.sc[SC_DLEN] = code ? 0 : l.region;
+    a.sc[SC_DLEN + 1] = code ? 0 : l.ptr_bytes;
+    a.sc[SC_CRC] = 0;
+    a.bsum[a.nblocks] = l.region;
+    a.start[a.n] = l.region;
+    /* the count heads the pointer section and is part of its span */
+    if (!code)
+        *reinterpret_cast<uint64_t *>(a.out + l.ptr_off) = mem_be64(a.n);
+}
+
+__global__ __launch_bounds__(WG) void pack_prefix_kernel(Pack a)
+{
+    __shared__ uint64_t s_scan[WG / 64];
+    if (a.sc[SC_CODE] != 0)
+        return;
+    uint64_t *ptrs = reinterpret_cast<uint64_t *>(a.out + a.sc[SC_PTR_OFF]) + 1;
+    const uint64_t first = (uint64_t)blockIdx.x * BLOCK_RECS;
+    uint64_t carry = a.bsum[blockIdx.x];
+#pragma unroll
+    for (uint32_t k = 0; k < PER; ++k) {
+        const uint64_t i = first + k * WG + threadIdx.x;
+        bool bad;
+        const uint64_t len = len_of(a, i, &bad);
+        uint64_t total;
+        const uint64_t at = carry + wg_scan_sat(s_scan, len, total);
+        if (i < a.n) {
+            a.start[i] = at;
+            ptrs[i] = mem_be64(HDR + at);
+        }
+        carry += total;
+    }
+}
+
+/* The word at rel of record r: generated, or gathered from the source. */
+__device__ inline uint64_t record_word(const Pack &a, const zscrc_zs_record &r, uint64_t rel)
+{
+    const Piece pc = piece_at(r, rel);
+    return pc.n ? gather8(a.src + pc.src_off, pc.n) : pc.word;
+}
+
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(WG) void pack_copy_kernel(Pack a)
+{
+    __shared__ uint64_t s_start[LDS_STARTS];
+    if (a.sc[SC_CODE] != 0)
+        return;
+    const uint64_t region = a.sc[SC_REGION];
+    if (region == 0)
+        return;
+    const uint64_t T = a.tile, ntiles = tile_count(T, region);
+    const uint64_t per = (ntiles + gridDim.x - 1) / gridDim.x;
+    const uint64_t t0 = (uint64_t)blockIdx.x * per;
+    const uint64_t t1 = t0 + per < ntiles ? t0 + per : ntiles;
+    if (t0 >= t1)
+        return;
+    uint64_t lo, hi;
+    tile_range(t0, T, region, &lo, &hi);
+    /* the first record that reaches into the run's first tile */
+    uint64_t rec0 = find_rec(a.start, a.n, lo);
+    for (uint64_t t = t0; t < t1; ++t) {
+        tile_range(t, T, region, &lo, &hi);
+        /* s_start[j] = start[rec0 + j] up to the first one at or past hi (start[n] = region is) */
+        uint32_t m = 0;
+        for (uint32_t base = 0; base < LDS_STARTS; base += WG) {
+            const uint64_t idx = rec0 + base + threadIdx.x;
+            const uint64_t s = a.start[idx < a.n ? idx : a.n];
+            s_start[base + threadIdx.x] = s;
+            const uint32_t c = (uint32_t)__syncthreads_count(s < hi);
+            m += c;
+            if (c < WG)
+                break;
+        }
+        /* 16-byte words of the tile, file offset f; the region is [40, 40 + region):
+         * a word half outside it is an 8-byte store of the half inside */
+        const uint64_t f0 = t * T;
+        for (uint64_t w = threadIdx.x; w < T / 16; w += WG) {
+            const uint64_t f = f0 + 16 * w;
+            if (f + 16 <= HDR)
+                continue;
+            if (f >= HDR + hi)
+                break;
+            const bool in0 = f >= HDR, in1 = f + 8 < HDR + hi;
+            /* one search a 16-byte word: its second half lies in the same
+             * record or, where that ends in between, at the next one's start */
+            const uint64_t p = in0 ? f - HDR : f + 8 - HDR;
+            uint64_t j = find_rec(s_start, m, p);
+            zscrc_zs_record r = a.recs[rec0 + j];
+            uint64_t v0 = 0, v1 = 0;
+            if (in0) {
+                v0 = record_word(a, r, p - s_start[j]);
+                if (in1 && p + 8 >= s_start[j + 1])
+                    r = a.recs[rec0 + ++j];
+            }
+            if (in1)
+                v1 = record_word(a, r, f + 8 - HDR - s_start[j]);
+            if (in0 && in1) {
+                u64x2 v;
+                v.x = v0;
+                v.y = v1;
+                *reinterpret_cast<u64x2 *>(a.out + f) = v;
+            } else if (in0) {
+                *reinterpret_cast<uint64_t *>(a.out + f) = v0;
+            } else {
+                *reinterpret_cast<uint64_t *>(a.out + f + 8) = v1;
+            }
+        }
+        /* the next tile starts at hi: in record rec0 + m - 1, or at rec0 + m's first byte */
+        const bool at_start = s_start[m] == hi;
+        __syncthreads(); /* s_start is rewritten by the next tile */
+        rec0 += at_start ? m : m - 1;
+    }
+}
+
+__global__ __launch_bounds__(64) void pack_seal_kernel(Pack a, Header h)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0 || a.sc[SC_CODE] != 0)
+        return;
+    const uint64_t region = a.sc[SC_REGION], ptr_off = a.sc[SC_PTR_OFF], ptr_bytes = 8 * (a.n + 1);
+    const uint32_t *crc = reinterpret_cast<const uint32_t *>(a.sc + SC_CRC);
+    uint64_t *out = reinterpret_cast<uint64_t *>(a.out);
+    uint64_t w[3];
+    uint32_t commit_crc, final_crc;
+    int k = commit_words(crc[0], region, false, w, &commit_crc);
+    for (int i = 0; i < k; ++i)
+        out[(HDR + region) / 8 + i] = w[i];
+    k = commit_words(crc[1], ptr_bytes, true, w, &final_crc);
+    for (int i = 0; i < k; ++i)
+        out[(ptr_off + ptr_bytes) / 8 + i] = w[i];
+    for (int i = 0; i < 5; ++i)
+        out[i] = h.w[i];
+    a.res[4] = crc[0];
+    a.res[5] = crc[1];
+    a.res[6] = commit_crc;
+    a.res[7] = final_crc;
+}
+
+bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
+
+/* The tile of a call; 0 = a bad option. */
+uint64_t tile_of(const zscrc_pack_opts *o)
+{
+    const uint64_t t = o && o->tile_bytes ? o->tile_bytes : DEF_TILE;
+    return pow2(t) && t >= TILE_MIN && t <= TILE_MAX ? t : 0;
+}
+
+uint64_t blocks_of(uint64_t n) { return (n + BLOCK_RECS - 1) / BLOCK_RECS; }
+
+size_t scratch_need(uint64_t n)
+{
+    return (size_t)(((SC_WORDS + blocks_of(n) + 1 + n + 1) * 8 + 15) & ~15ull);
+}
+
+int launch(Pack &a, void *scratch, const Header &h, hipStream_t s)
+{
+    a.sc = static_cast<uint64_t *>(scratch);
+    a.bsum = a.sc + SC_WORDS;
+    a.start = a.bsum + a.nblocks + 1;
+    if (a.n) {
+        if (hipMemsetAsync(a.sc + SC_BAD, 0xFF, 8, s) != hipSuccess)
+            return ZSCRC_EHIP;
+        hipLaunchKernelGGL(pack_size_kernel, dim3((unsigned)a.nblocks), dim3(WG), 0, s, a);
+    }
+    hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(WG), 0, s, a);
+    if (hipGetLastError() != hipSuccess)
+        return ZSCRC_EHIP;
+    /* no file fits fewer than 64 bytes: the sizing call ends here */
+    if (a.out_cap < 64)
+        return ZSCRC_OK;
+    if (a.n) {
+        int dev = 0, ncu = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
+            return ZSCRC_EHIP;
+        hipLaunchKernelGGL(pack_prefix_kernel, dim3((unsigned)a.nblocks), dim3(WG), 0, s, a);
+        /* the region's size is on the device only: a grid for the most the
+         * output can hold, capped; a workgroup takes a run of the tiles there are */
+        uint64_t g = (a.out_cap + a.tile - 1) / a.tile;
+        const uint64_t gmax = (uint64_t)ncu * COPY_WG_PER_CU;
+        if (g > gmax)
+            g = gmax;
+        hipLaunchKernelGGL(pack_copy_kernel, dim3((unsigned)g), dim3(WG), 0, s, a);
+    }
+    if (hipGetLastError() != hipSuccess)
+        return ZSCRC_EHIP;
+    const int rc = zscrc_device_batch(a.out, a.sc + SC_DOFF, a.sc + SC_DLEN, nullptr,
+                                      reinterpret_cast<uint32_t *>(a.sc + SC_CRC), 2, 0, s);
+    if (rc)
+        return rc;
+    hipLaunchKernelGGL(pack_seal_kernel, dim3(1), dim3(64), 0, s, a, h);
+    return hipGetLastError() == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+}
+
+} /* namespace */
+
+extern "C" {
+
+uint64_t zscrc_device_pack_bound(uint64_t n, uint64_t sum_key_len, uint64_t sum_val_len)
+{
+    uint64_t b;
+    if (__builtin_mul_overflow(n, (uint64_t)62, &b) || __builtin_add_overflow(b, (uint64_t)120, &b) ||
+        __builtin_add_overflow(b, sum_key_len, &b) || __builtin_add_overflow(b, sum_val_len, &b))
+        return 0;
+    return b;
+}
+
+size_t zscrc_device_pack_scratch_bytes(size_t n, const zscrc_pack_opts *opts)
+{
+    if (!tile_of(opts) || n > N_MAX)
+        return 0;
+    return scratch_need(n);
+}
+
+int zscrc_device_pack(const void *d_src, uint64_t src_size, const struct zscrc_zs_record *d_recs, size_t n,
+                      const uint8_t uuid[16], uint32_t startidx, uint32_t endidx, void *d_out, uint64_t out_cap,
+                      uint64_t *d_res, void *scratch, const zscrc_pack_opts *opts, unsigned flags, void *stream)
+{
+    const uintptr_t so = reinterpret_cast<uintptr_t>(d_src), oo = reinterpret_cast<uintptr_t>(d_out);
+    const uint64_t tile = tile_of(opts);
+    if (!d_res || !uuid || (n && !d_recs) || (!d_src && src_size) || (out_cap && !d_out) || (oo & 15) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 15) || flags || !tile || n > N_MAX || src_size > SRC_MAX ||
+        out_cap > UINTPTR_MAX - oo || src_size > UINTPTR_MAX - so)
+        return ZSCRC_EINVAL;
+    if (out_cap && src_size && oo < so + src_size && so < oo + out_cap)
+        return ZSCRC_EINVAL;
+    Pack a{};
+    a.src = static_cast<const uint8_t *>(d_src);
+    a.src_size = src_size;
+    a.recs = d_recs;
+    a.n = n;
+    a.out = static_cast<uint8_t *>(d_out);
+    a.out_cap = out_cap;
+    a.res = d_res;
+    a.nblocks = blocks_of(n);
+    a.tile = tile;
+    const Header h = header_words(uuid, startidx, endidx);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (scratch)
+        return launch(a, scratch, h, s);
+    zs::Scratch *sc = zs::device_scratch();
+    if (!sc)
+        return ZSCRC_ENODEV;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    const int arc = zs::scratch_acquire(*sc, scratch_need(n), s);
+    if (arc)
+        return arc;
+    return zs::scratch_done(*sc, s, launch(a, sc->p, h, s));
+}
+
+} /* extern "C" */

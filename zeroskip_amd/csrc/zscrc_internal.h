@@ -3,7 +3,10 @@
 #define ZSCRC_INTERNAL_H
 
 #include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include <mutex>
 
 /* Global operator-table block (uint32 words), built on the host per device. */
 enum {
@@ -32,6 +35,33 @@ inline bool same_stream(hipStream_t a, hipStream_t b)
         b = nullptr;
     return a == b && a != hipStreamPerThread;
 }
+
+/* The walk's library-owned scratch (zscrc_walk.hip), one buffer per device,
+ * shared by every call there that passes no scratch of its own
+ * (zscrc_device_walk, _records, _walk_multi, zscrc_device_pack): a call on
+ * another stream than the last user's waits for that user's work. */
+struct Scratch {
+    std::mutex mu;
+    void *p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t last = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool last_valid = false;
+    /* zscrc_device_walk_multi: pinned staging of the image descriptors on
+     * their way to the device, reused once its last copy has run (staged) */
+    void *pin = nullptr;
+    size_t pin_bytes = 0;
+    hipEvent_t staged = nullptr;
+    bool staged_valid = false;
+};
+/* The current device's scratch; NULL = no device the library can serve. */
+Scratch *device_scratch();
+/* With sc.mu held: the library scratch grown to `need` bytes, and the stream
+ * made to wait for the buffer's last user on another stream. */
+int scratch_acquire(Scratch &sc, size_t need, hipStream_t s);
+/* With sc.mu held, after the launches (their status: rc): the event the
+ * buffer's next user waits for. */
+int scratch_done(Scratch &sc, hipStream_t s, int rc);
 
 struct RecDesc;
 

@@ -61,8 +61,13 @@
 
 namespace {
 
+using zs::device_scratch;
+using zs::Scratch;
+using zs::scratch_acquire;
+using zs::scratch_done;
+
 constexpr int WG = 256;
-constexpr uint32_t TILE_SLOTS_MAX = 2048;             /* 16 KiB of image per tile */
+constexpr uint32_t TILE_SLOTS_MAX = 2048;            /* 16 KiB of image per tile */
 constexpr uint32_t SPT = TILE_SLOTS_MAX / WG;         /* a thread's slots of a tile: i = thread + j * WG */
 constexpr uint64_t DEF_BLOCK = 1ull << 20, DEF_TILE = 16384;
 constexpr uint64_t BLOCK_MAX = 1ull << 30;
@@ -1110,34 +1115,22 @@ bool serial_only(const Walk &w, unsigned flags) { return (flags & ZSCRC_WALK_SER
 
 size_t scratch_bytes(const Walk &w) { return (size_t)(w.nblocks * sizeof(Entry) + w.ns * 8); }
 
-/* Library-owned scratch, one buffer per device, shared by every call there: a
+/* Library-owned scratch (zs::Scratch, zscrc_internal.h), one buffer per device,
+ * shared by every call there -- the device packer's (zscrc_devpack.hip) too: a
  * call on another stream than the last user's waits for that user's work. */
 constexpr int MAX_DEV = 64;
-struct Scratch {
-    std::mutex mu;
-    void *p = nullptr;
-    size_t bytes = 0;
-    hipEvent_t last = nullptr;
-    hipStream_t last_stream = nullptr;
-    bool last_valid = false;
-    /* zscrc_device_walk_multi: pinned staging of the image descriptors on
-     * their way to the device, reused once its last copy has run (staged) */
-    void *pin = nullptr;
-    size_t pin_bytes = 0;
-    hipEvent_t staged = nullptr;
-    bool staged_valid = false;
-};
 Scratch g_scratch[MAX_DEV];
 
-/* The current device's scratch; NULL = no device the library can serve. */
+} /* namespace */
+
+namespace zs {
+
 Scratch *device_scratch()
 {
     int dev = -1;
     return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_DEV ? &g_scratch[dev] : nullptr;
 }
 
-/* With sc.mu held: the library scratch grown to `need` bytes, and the stream
- * made to wait for the buffer's last user on another stream. */
 int scratch_acquire(Scratch &sc, size_t need, hipStream_t s)
 {
     if (sc.bytes < need) {
@@ -1159,8 +1152,6 @@ int scratch_acquire(Scratch &sc, size_t need, hipStream_t s)
     return ZSCRC_OK;
 }
 
-/* With sc.mu held, after the launches (their status: rc): the event the
- * buffer's next user waits for. */
 int scratch_done(Scratch &sc, hipStream_t s, int rc)
 {
     if (!sc.last && hipEventCreateWithFlags(&sc.last, hipEventDisableTiming) != hipSuccess)
@@ -1171,6 +1162,10 @@ int scratch_done(Scratch &sc, hipStream_t s, int rc)
         return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
     return rc;
 }
+
+} /* namespace zs */
+
+namespace {
 
 /* records: the record lister's instances instead of the commit walk's. */
 int launch(const Walk &w, unsigned flags, hipStream_t s, bool records)

@@ -145,6 +145,73 @@ def repack_dir(dbdir: str, threads: int = 0, fsync: bool = False, reference_comp
     return rep.as_dict()
 
 
+class PackOpts(ctypes.Structure):
+    """zscrc_pack_opts (include/zscrc.h); 0 = the default."""
+    _fields_ = [("tile_bytes", ctypes.c_uint64)]
+
+
+PACK_RES_WORDS = 8  # ZSCRC_PACK_RES_WORDS
+PACK_OVERFLOW = 3  # ZSCRC_ZS_OVERFLOW in res[0]
+
+
+def device_pack_bound(n: int, sum_key_len: int, sum_val_len: int) -> int:
+    """An upper bound on the packed file's size from the record lister's
+    res[1], res[4], res[5] (zscrc_device_pack_bound); 0 if it wraps."""
+    return lib().zscrc_device_pack_bound(n, sum_key_len, sum_val_len)
+
+
+def device_pack_scratch_bytes(n: int, tile_bytes: int = 0) -> int:
+    """zscrc_device_pack_scratch_bytes; 0 = a bad option."""
+    return lib().zscrc_device_pack_scratch_bytes(n, ctypes.byref(PackOpts(tile_bytes)))
+
+
+def device_pack(d_src, recs, uuid: bytes, startidx: int = 0, endidx: int = 0, out=None, tile_bytes: int = 0,
+                scratch=None):
+    """The packed file of a device-resident record list, written on the GPU
+    (zscrc_device_pack): (image, res).  d_src: the uint8 device tensor the
+    records' offsets point into; recs: an int64 [n, 4] device tensor (key_off,
+    key_len, val_off or -1 for a delete, val_len) such as
+    zsfile.device_records returns, sliced to its count; records are written in
+    the order given.  res: int64 device tensor [code (0 written, 3 the file
+    does not fit `out`, -1 a record outside d_src), n or the first bad index,
+    file_bytes, region_bytes, region_crc, pointers_crc, commit_crc, final_crc].
+    out=None: a sizing call, one read of res[2] (the wrapper's only
+    synchronisation) and an output of exactly that size; image is None when a
+    record is bad.  out given (a 16-byte aligned uint8 device tensor): one
+    asynchronous call on the current stream, image = out (file_bytes of it are
+    the file when res[0] == 0).  scratch: a 16-byte aligned uint8 tensor of
+    device_pack_scratch_bytes(n) bytes (default: the library's own)."""
+    import torch
+
+    assert len(uuid) == 16
+    dev = d_src.device
+    n = int(recs.shape[0])
+    assert recs.dtype == torch.int64 and recs.is_contiguous() and (n == 0 or recs.shape[1] == 4)
+    res = torch.empty(PACK_RES_WORDS, dtype=torch.int64, device=dev)
+    opts = PackOpts(tile_bytes)
+    src_bytes = d_src.numel() * d_src.element_size()
+
+    def call(o):
+        cap = 0 if o is None else o.numel() * o.element_size()
+        with torch.cuda.device(dev):
+            check(lib().zscrc_device_pack(
+                d_src.data_ptr() if src_bytes else None, src_bytes, recs.data_ptr() if n else None, n, bytes(uuid),
+                startidx, endidx, o.data_ptr() if cap else None, cap, res.data_ptr(),
+                None if scratch is None else scratch.data_ptr(), ctypes.byref(opts), 0,
+                torch.cuda.current_stream(dev).cuda_stream), "zscrc_device_pack")
+
+    if out is not None:
+        call(out)
+        return out, res
+    call(None)
+    code, _, file_bytes = (int(v) for v in res[:3].cpu())
+    if code != PACK_OVERFLOW:
+        return None, res
+    out = torch.empty(file_bytes, dtype=torch.uint8, device=dev)
+    call(out)
+    return out, res
+
+
 def records(image, kind: int):
     """(key_off, key_len, val_off, val_len) uint64 arrays of a file image's
     records (zscrc_zs_records); val_off == 2**64-1 marks a delete."""
