@@ -675,6 +675,74 @@ int zscrc_device_pack(const void *d_src, uint64_t src_size,
                       void *d_out, uint64_t out_cap, uint64_t *d_res, void *scratch,
                       const zscrc_pack_opts *opts, unsigned flags, void *stream);
 
+/* The key merge on the device: the sort by key and the winner loop of
+ * zscrc_zs_repack for record lists that live in device memory -- the step
+ * between zscrc_device_records and zscrc_device_pack, without a key crossing
+ * PCIe.  The input is the concatenation of the k lists in the order given:
+ * record j of list l has the sequence number seq = n_0 + .. + n_(l-1) + j and
+ * its key_off (and its val_off, unless that is ZSCRC_ZS_DELETED) has base_l
+ * added, so that every list of an arena of several images points into the one
+ * d_src.  The order is memcmp over the shorter key's length with unsigned
+ * bytes, then the shorter key first (the reference's memcmp_raw), ties broken
+ * by seq; of every run of equal keys the record with the largest seq wins.
+ * Branch 1 of a repack passes its finalised files oldest first; branch 2 passes
+ * the newer packed file first and the older one last, with
+ * ZSCRC_MERGE_DROP_DELETES: a winning delete is then dropped instead of kept.
+ * d_out receives the winners in key order, each the input entry's four words
+ * rebased (val_len of a delete as it came): a list zscrc_device_pack takes as
+ * it is over the same d_src.
+ * Launches in stream order (one thread a record: rebase, check, sort entry; one
+ * workgroup's sort of every tile in LDS; ceil(log2(tiles)) merge passes cut by
+ * merge-path searches; winner flags and block counts, one workgroup's scan,
+ * the scatter); every grid is sized on the host from n_total, no workgroup
+ * waits for another.  tile_records: the records one workgroup sorts and later
+ * merges per work item, a power of two, 64 <= tile <= 2048, 0 = the default
+ * (2048).
+ * Limits: n_total <= 2^31 - 1, k <= ZSCRC_WALK_MULTI_MAX, src_size <= 2^62. */
+typedef struct zscrc_merge_list {
+    const struct zscrc_zs_record *d_recs;  /* device, n entries as zscrc_device_records writes them */
+    uint64_t n;
+    uint64_t base;                         /* added to key_off, and to val_off unless ZSCRC_ZS_DELETED */
+} zscrc_merge_list;
+typedef struct zscrc_merge_opts { uint32_t tile_records; } zscrc_merge_opts;  /* NULL / 0 = default */
+#define ZSCRC_MERGE_DROP_DELETES 1u
+#define ZSCRC_MERGE_RES_WORDS 8
+/* Bytes of scratch zscrc_device_merge needs for n_total records in any number
+ * of lists (only the descriptors of lists that are not empty go to the device,
+ * at most n_total of them): 65 bytes a record, 24 a list and a few words; a
+ * multiple of 16, monotone in n_total.  0 = a bad option or n_total above the
+ * limit. */
+size_t zscrc_device_merge_scratch_bytes(size_t n_total, const zscrc_merge_opts *opts);
+/* Asynchronous on `stream`: nothing is copied to the host, nothing waits (the
+ * list descriptors reach the device through the library's pinned staging, as
+ * zscrc_device_walk_multi's do).  d_res (device, ZSCRC_MERGE_RES_WORDS words):
+ *   [0] 0; ZSCRC_ZS_OVERFLOW = more winners than cap (entries i < min(n_out,
+ *       cap) are written and none past that; cap 0 with d_out NULL is the
+ *       sizing call); (uint64_t)(int64_t)ZSCRC_EINVAL = some rebased record
+ *       does not lie inside [0, src_size) (checked against the bytes left,
+ *       never with an add that can wrap): no entry of d_out is written
+ *   [1] n_out, the number of winners; on a bad record the smallest seq of one
+ *   [2] n_total
+ *   [3] the deletes among the n_out winners (0 with DROP_DELETES)
+ *   [4] the sum of key_len over the winners
+ *   [5] the sum of val_len over the winners that are not deletes
+ *       ([1], [4], [5]: what zscrc_device_pack_bound takes)
+ *   [6] records superseded by a later one of their key
+ *   [7] winning deletes dropped
+ * [1] + [6] + [7] == [2] whenever [0] is 0 or OVERFLOW; on a bad record
+ * [3] .. [7] are 0.
+ * scratch: 16-byte aligned device memory of zscrc_device_merge_scratch_bytes
+ * bytes, or NULL for the walk's per-device library scratch (zscrc_device_walk:
+ * stream-ordered between calls, kept until zscrc_release_cache).
+ * ZSCRC_EINVAL before any device call: d_res NULL; k > 0 with lists NULL; a
+ * list with n > 0 and d_recs NULL; d_src NULL with src_size > 0; cap > 0 with
+ * d_out NULL; scratch not 16-byte aligned; an unknown flag; a bad option;
+ * n_total, k or src_size above its limit. */
+int zscrc_device_merge(const void *d_src, uint64_t src_size,
+                       const zscrc_merge_list *lists, size_t k,
+                       struct zscrc_zs_record *d_out, size_t cap, uint64_t *d_res,
+                       void *scratch, const zscrc_merge_opts *opts, unsigned flags, void *stream);
+
 /* `consistent` for one process / one GPU (zsdb_consistent,
  * src/zeroskip.c:1399-1407, and tool/cmd-consistent.c:23-49 are stubs in the
  * reference): every .zsdb / header / commit CRC of the DB directory,

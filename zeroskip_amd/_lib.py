@@ -110,6 +110,8 @@ SIGNATURES = {
     "zscrc_device_pack_scratch_bytes": (_sz, [_sz, _vp]),
     "zscrc_device_pack": (_int, [_vp, _u64, _vp, _sz, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, ctypes.c_uint,
                                  _vp]),
+    "zscrc_device_merge_scratch_bytes": (_sz, [_sz, _vp]),
+    "zscrc_device_merge": (_int, [_vp, _u64, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.c_uint, _vp]),
 }
 ABI_VERSION = 4  # include/zscrc.h ZSCRC_ABI_VERSION
 

@@ -62,6 +62,12 @@ int scratch_acquire(Scratch &sc, size_t need, hipStream_t s);
 /* With sc.mu held, after the launches (their status: rc): the event the
  * buffer's next user waits for. */
 int scratch_done(Scratch &sc, hipStream_t s, int rc);
+/* With sc.mu held: the pinned staging (sc.pin) grown to `bytes` and free to be
+ * filled, its last copy having run. */
+int stage_begin(Scratch &sc, size_t bytes);
+/* With sc.mu held: the staging's first `bytes` copied to d_dst (device) in
+ * stream order. */
+int stage_copy(Scratch &sc, void *d_dst, size_t bytes, hipStream_t s);
 
 struct RecDesc;
 

@@ -1,0 +1,497 @@
+/*
+ * zscrc_merge.hip -- the key merge of zscrc_zs_repack on the device:
+ * zscrc_device_merge sorts device-resident record lists by key and keeps the
+ * winner of every key, with no key crossing PCIe ("The merge on
+ * the device").  The order arithmetic is zscrc_merge_order.h's, shared with
+ * the host.
+ *
+ * A comparison merge sort over 16-byte sort entries {key prefix, seq, length}.
+ * Launches, all in stream order, no workgroup waiting for another one:
+ *
+ *   merge_gather_kernel   one thread per input record: its list by binary
+ *                         search of the staged prefix counts, the record
+ *                         rebased and checked against the source (the smallest
+ *                         bad seq by an integer min), the sort entry
+ *   merge_sort_kernel     one workgroup per tile: the tile's entries and each
+ *                         key's second word in LDS, a bitonic network
+ *   merge_pass_kernel     ceil(log2(tiles)) times, ping-pong between two entry
+ *                         arrays: a workgroup produces one tile of output from
+ *                         two adjacent sorted runs -- two merge-path searches
+ *                         cut its pieces of both, they are staged in LDS, every
+ *                         thread finds its own cut there and merges a few
+ *                         entries; a last run without a partner is copied
+ *   merge_flag_kernel     one workgroup per BLOCK_RECS entries: winner,
+ *                         superseded or dropped delete; the block's winners,
+ *                         the totals of the result words by integer adds
+ *   merge_scan_kernel     one workgroup: the block counts to their exclusive
+ *                         prefix, the result words
+ *   merge_scatter_kernel  one workgroup per block: the winners' rebased
+ *                         records to their places in the output
+ *
+ * Every grid and the number of passes come from n_total on the host.  A bad
+ * record makes every launch after the gather return at once.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+
+#include "../../include/zscrc.h"
+#include "zscrc_internal.h"
+#include "zscrc_merge_order.h"
+
+namespace {
+
+using namespace zsmerge;
+using zspack::U64_MAX;
+
+constexpr int WG = 256;
+constexpr uint32_t PER = 4;                       /* entries a thread of a block */
+constexpr uint32_t BLOCK_RECS = WG * PER;
+constexpr uint64_t N_MAX = (1ull << 31) - 1;      /* records of one call */
+/* the default: measured, DESIGN.md 2.6 (sorted input is 5 % slower than at
+ * 1,024, shuffled input 21 % faster) */
+constexpr uint32_t DEF_TILE = 2048, TILE_MIN = 64, TILE_MAX = 2048;
+
+/* A list on the device: its records, the seq of its first one, its base.
+ * Entry k (one past the last list) holds n_total. */
+struct ListD {
+    const zscrc_zs_record *recs;
+    uint64_t first;
+    uint64_t base;
+};
+struct Firsts {
+    const ListD *d;
+    __host__ __device__ uint64_t operator[](uint64_t i) const { return d[i].first; }
+};
+
+/* scratch words */
+enum { SC_BAD = 0, SC_DELETES = 1, SC_SUMK = 2, SC_SUMV = 3, SC_DROPPED = 4, SC_WORDS = 16 };
+
+struct Merge {
+    const uint8_t *src;
+    uint64_t src_size;
+    const ListD *lists;
+    uint32_t k;        /* lists that are not empty */
+    uint32_t n;        /* n_total */
+    uint32_t tile;
+    uint32_t drop;
+    uint32_t nblocks;
+    unsigned long long *sc; /* SC_WORDS words */
+    zscrc_zs_record *rb;    /* the rebased records by seq */
+    Entry *e0, *e1;
+    uint32_t *bcount;       /* nblocks + 1 */
+    uint8_t *flags;         /* n */
+    const Entry *sorted;    /* e0 or e1: where the last pass left the entries */
+    zscrc_zs_record *out;
+    uint64_t cap;
+    uint64_t *res;
+};
+
+struct KeyLess {
+    Keys K;
+    __device__ bool operator()(const Entry &a, const Entry &b) const { return less(K, a, b); }
+};
+
+__device__ inline bool is_bad(const Merge &a) { return a.sc[SC_BAD] != U64_MAX; }
+
+__global__ __launch_bounds__(WG) void merge_gather_kernel(Merge a)
+{
+    const uint64_t seq = (uint64_t)blockIdx.x * WG + threadIdx.x;
+    if (seq >= a.n)
+        return;
+    const ListD l = a.lists[zspack::find_rec(Firsts{a.lists}, a.k, seq)];
+    zscrc_zs_record r = l.recs[seq - l.first];
+    if (!rebase(r, l.base, a.src_size)) {
+        atomicMin(a.sc + SC_BAD, (unsigned long long)seq);
+        return;
+    }
+    a.rb[seq] = r;
+    a.e0[seq] = make_entry(a.src, r, (uint32_t)seq);
+}
+
+__global__ __launch_bounds__(WG) void merge_sort_kernel(Merge a)
+{
+    extern __shared__ __align__(16) uint8_t lds[];
+    if (is_bad(a))
+        return;
+    const uint32_t T = a.tile;
+    Entry *s_e = reinterpret_cast<Entry *>(lds);
+    uint64_t *s_w = reinterpret_cast<uint64_t *>(s_e + T);
+    const Keys K{a.src, a.rb};
+    const uint64_t first = (uint64_t)blockIdx.x * T;
+    for (uint32_t i = threadIdx.x; i < T; i += WG) {
+        Entry e{0, SEQ_PAD, 0};
+        uint64_t w = 0;
+        if (first + i < a.n) {
+            e = a.e0[first + i];
+            if (e.len > 8)
+                w = key_word(K.src, K.recs[e.seq].key_off, K.recs[e.seq].key_len, 8);
+        }
+        s_e[i] = e;
+        s_w[i] = w;
+    }
+    __syncthreads();
+    for (uint32_t k = 2; k <= T; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = threadIdx.x; t < T / 2; t += WG) {
+                uint32_t lo;
+                bool up;
+                bitonic_pair(t, k, j, &lo, &up);
+                const Entry x = s_e[lo], y = s_e[lo + j];
+                const uint64_t wx = s_w[lo], wy = s_w[lo + j];
+                if (less_tile(K, y, wy, x, wx) == up) {
+                    s_e[lo] = y;
+                    s_e[lo + j] = x;
+                    s_w[lo] = wy;
+                    s_w[lo + j] = wx;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = threadIdx.x; i < T; i += WG)
+        if (first + i < a.n)
+            a.e0[first + i] = s_e[i];
+}
+
+/* One pass: runs of `run` entries of `in` merged pairwise into `out`. */
+__global__ __launch_bounds__(WG) void merge_pass_kernel(Merge a, const Entry *in, Entry *out, uint32_t run)
+{
+    extern __shared__ __align__(16) uint8_t lds[];
+    __shared__ uint32_t s_cut[2];
+    if (is_bad(a))
+        return;
+    Entry *s = reinterpret_cast<Entry *>(lds);
+    const uint32_t T = a.tile, n = a.n;
+    const uint64_t o0 = (uint64_t)blockIdx.x * T;          /* the output tile [o0, o0 + cnt) */
+    const uint32_t cnt = n - o0 < T ? (uint32_t)(n - o0) : T;
+    const uint64_t a0 = o0 / (2ull * run) * (2ull * run);  /* the pair of runs it lies in */
+    const uint32_t na = n - a0 < run ? (uint32_t)(n - a0) : run;
+    const uint64_t b0 = a0 + na;
+    const uint32_t nb = n - b0 < run ? (uint32_t)(n - b0) : run;
+    if (nb == 0) {
+        for (uint32_t i = threadIdx.x; i < cnt; i += WG)
+            out[o0 + i] = in[o0 + i];
+        return;
+    }
+    const KeyLess lt{Keys{a.src, a.rb}};
+    const uint32_t d0 = (uint32_t)(o0 - a0);
+    if (threadIdx.x < 2)
+        s_cut[threadIdx.x] = diag_search(in + a0, na, in + b0, nb, threadIdx.x ? d0 + cnt : d0, lt);
+    __syncthreads();
+    const uint32_t i0 = s_cut[0], ca = s_cut[1] - i0, cb = cnt - ca;
+    const Entry *pa = in + a0 + i0, *pb = in + b0 + (d0 - i0);
+    for (uint32_t i = threadIdx.x; i < cnt; i += WG)
+        s[i] = i < ca ? pa[i] : pb[i - ca];
+    __syncthreads();
+    const uint32_t vt = (T + WG - 1) / WG, d = threadIdx.x * vt;
+    if (d >= cnt)
+        return;
+    const Entry *sa = s, *sb = s + ca;
+    uint32_t i = diag_search(sa, ca, sb, cb, d, lt), j = d - i;
+    for (uint32_t v = 0; v < vt && d + v < cnt; ++v) {
+        const bool take_a = j >= cb || (i < ca && !lt(sb[j], sa[i]));
+        out[o0 + d + v] = take_a ? sa[i++] : sb[j++];
+    }
+}
+
+/* Sum of one value a thread over the workgroup, in every thread.  s: WG / 64
+ * words of LDS, free again on return. */
+__device__ inline uint64_t wg_sum(uint64_t *s, uint64_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        v += __shfl_xor(v, d, 64);
+    if ((threadIdx.x & 63) == 0)
+        s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t all = 0;
+#pragma unroll
+    for (unsigned w = 0; w < WG / 64; ++w)
+        all += s[w];
+    __syncthreads();
+    return all;
+}
+
+/* Exclusive prefix sum of one value a thread over the workgroup; total = the
+ * sum of all.  s as for wg_sum. */
+__device__ inline uint64_t wg_scan(uint64_t *s, uint64_t mine, uint64_t &total)
+{
+    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t inc = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t o = __shfl_up(inc, d, 64);
+        if (lane >= (unsigned)d)
+            inc += o;
+    }
+    if (lane == 63)
+        s[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+#pragma unroll
+    for (unsigned w = 0; w < WG / 64; ++w) {
+        if (w < wave)
+            before += s[w];
+        all += s[w];
+    }
+    __syncthreads();
+    total = all;
+    return before + inc - mine;
+}
+
+__global__ __launch_bounds__(WG) void merge_flag_kernel(Merge a)
+{
+    __shared__ uint64_t s_part[WG / 64];
+    if (is_bad(a))
+        return;
+    const Keys K{a.src, a.rb};
+    const uint64_t first = (uint64_t)blockIdx.x * BLOCK_RECS;
+    uint64_t winners = 0, deletes = 0, sumk = 0, sumv = 0, dropped = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < PER; ++k) {
+        const uint64_t i = first + k * WG + threadIdx.x;
+        if (i >= a.n)
+            break;
+        const int f = winner_flag(K, a.sorted, i, a.n, a.drop != 0);
+        a.flags[i] = (uint8_t)f;
+        if (f == F_WINNER) {
+            const zscrc_zs_record r = a.rb[a.sorted[i].seq];
+            ++winners;
+            sumk += r.key_len;
+            if (is_delete(r))
+                ++deletes;
+            else
+                sumv += r.val_len;
+        } else if (f == F_DROPPED) {
+            ++dropped;
+        }
+    }
+    winners = wg_sum(s_part, winners);
+    deletes = wg_sum(s_part, deletes);
+    sumk = wg_sum(s_part, sumk);
+    sumv = wg_sum(s_part, sumv);
+    dropped = wg_sum(s_part, dropped);
+    if (threadIdx.x != 0)
+        return;
+    a.bcount[blockIdx.x] = (uint32_t)winners;
+    if (deletes)
+        atomicAdd(a.sc + SC_DELETES, (unsigned long long)deletes);
+    if (sumk)
+        atomicAdd(a.sc + SC_SUMK, (unsigned long long)sumk);
+    if (sumv)
+        atomicAdd(a.sc + SC_SUMV, (unsigned long long)sumv);
+    if (dropped)
+        atomicAdd(a.sc + SC_DROPPED, (unsigned long long)dropped);
+}
+
+__global__ __launch_bounds__(WG) void merge_scan_kernel(Merge a)
+{
+    __shared__ uint64_t s_scan[WG / 64];
+    const uint64_t bad = a.n ? a.sc[SC_BAD] : U64_MAX;
+    uint64_t carry = 0;
+    if (bad == U64_MAX) {
+        for (uint64_t c = 0; c < a.nblocks; c += BLOCK_RECS) {
+            const uint64_t first = c + (uint64_t)threadIdx.x * PER;
+            uint64_t v[PER], mine = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < PER; ++k) {
+                v[k] = first + k < a.nblocks ? a.bcount[first + k] : 0;
+                mine += v[k];
+            }
+            uint64_t total;
+            uint64_t at = carry + wg_scan(s_scan, mine, total);
+#pragma unroll
+            for (uint32_t k = 0; k < PER; ++k) {
+                if (first + k < a.nblocks)
+                    a.bcount[first + k] = (uint32_t)at;
+                at += v[k];
+            }
+            carry += total;
+        }
+    }
+    if (threadIdx.x != 0)
+        return;
+    if (bad != U64_MAX) {
+        a.res[0] = (uint64_t)(int64_t)ZSCRC_EINVAL;
+        a.res[1] = bad;
+        a.res[2] = a.n;
+        for (int i = 3; i < ZSCRC_MERGE_RES_WORDS; ++i)
+            a.res[i] = 0;
+        return;
+    }
+    const uint64_t dropped = a.n ? a.sc[SC_DROPPED] : 0;
+    a.res[0] = carry > a.cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : 0;
+    a.res[1] = carry;
+    a.res[2] = a.n;
+    a.res[3] = a.n ? a.sc[SC_DELETES] : 0;
+    a.res[4] = a.n ? a.sc[SC_SUMK] : 0;
+    a.res[5] = a.n ? a.sc[SC_SUMV] : 0;
+    a.res[6] = a.n - carry - dropped;
+    a.res[7] = dropped;
+}
+
+__global__ __launch_bounds__(WG) void merge_scatter_kernel(Merge a)
+{
+    __shared__ uint64_t s_scan[WG / 64];
+    if (is_bad(a))
+        return;
+    const uint64_t first = (uint64_t)blockIdx.x * BLOCK_RECS;
+    uint64_t carry = a.bcount[blockIdx.x];
+    if (carry >= a.cap)
+        return;
+#pragma unroll
+    for (uint32_t k = 0; k < PER; ++k) {
+        const uint64_t i = first + k * WG + threadIdx.x;
+        const bool win = i < a.n && a.flags[i] == F_WINNER;
+        uint64_t total;
+        const uint64_t at = carry + wg_scan(s_scan, win, total);
+        if (win && at < a.cap)
+            a.out[at] = a.rb[a.sorted[i].seq];
+        carry += total;
+    }
+}
+
+/* The tile of a call; 0 = a bad option. */
+uint32_t tile_of(const zscrc_merge_opts *o)
+{
+    const uint32_t t = o && o->tile_records ? o->tile_records : DEF_TILE;
+    return (t & (t - 1)) == 0 && t >= TILE_MIN && t <= TILE_MAX ? t : 0;
+}
+
+constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+/* The pieces of the scratch for n records: the words, the descriptors of at
+ * most min(n, ZSCRC_WALK_MULTI_MAX) lists that are not empty and the entry
+ * that ends them, the rebased records, two entry arrays, the block counts,
+ * the flags. */
+struct Plan {
+    size_t lists_at, rb_at, e0_at, e1_at, bcount_at, flags_at, bytes;
+    uint32_t nblocks;
+};
+Plan plan_of(uint64_t n)
+{
+    Plan p;
+    const uint64_t kmax = n < ZSCRC_WALK_MULTI_MAX ? n : ZSCRC_WALK_MULTI_MAX;
+    p.nblocks = (uint32_t)((n + BLOCK_RECS - 1) / BLOCK_RECS);
+    p.lists_at = SC_WORDS * 8;
+    p.rb_at = p.lists_at + up16((kmax + 1) * sizeof(ListD));
+    p.e0_at = p.rb_at + n * sizeof(zscrc_zs_record);
+    p.e1_at = p.e0_at + n * sizeof(Entry);
+    p.bcount_at = p.e1_at + n * sizeof(Entry);
+    p.flags_at = p.bcount_at + up16((p.nblocks + 1) * 4);
+    p.bytes = p.flags_at + up16(n);
+    return p;
+}
+
+int launch(Merge &a, const Plan &p, void *scratch, zs::Scratch &sc, const zscrc_merge_list *lists, size_t k,
+           hipStream_t s)
+{
+    uint8_t *base = static_cast<uint8_t *>(scratch);
+    a.sc = reinterpret_cast<unsigned long long *>(base);
+    ListD *d_lists = reinterpret_cast<ListD *>(base + p.lists_at);
+    a.lists = d_lists;
+    a.rb = reinterpret_cast<zscrc_zs_record *>(base + p.rb_at);
+    a.e0 = reinterpret_cast<Entry *>(base + p.e0_at);
+    a.e1 = reinterpret_cast<Entry *>(base + p.e1_at);
+    a.bcount = reinterpret_cast<uint32_t *>(base + p.bcount_at);
+    a.flags = base + p.flags_at;
+    a.nblocks = p.nblocks;
+    a.sorted = a.e0;
+    if (a.n) {
+        /* the descriptors of the lists that hold records, through the pinned staging */
+        const size_t bytes = ((size_t)a.k + 1) * sizeof(ListD);
+        int rc = zs::stage_begin(sc, bytes);
+        if (rc)
+            return rc;
+        ListD *h = static_cast<ListD *>(sc.pin);
+        uint64_t first = 0;
+        for (size_t l = 0; l < k; ++l) {
+            if (!lists[l].n)
+                continue;
+            *h++ = ListD{lists[l].d_recs, first, lists[l].base};
+            first += lists[l].n;
+        }
+        *h = ListD{nullptr, first, 0};
+        rc = zs::stage_copy(sc, d_lists, bytes, s);
+        if (rc)
+            return rc;
+        if (hipMemsetAsync(a.sc, 0, SC_WORDS * 8, s) != hipSuccess ||
+            hipMemsetAsync(a.sc + SC_BAD, 0xFF, 8, s) != hipSuccess)
+            return ZSCRC_EHIP;
+        const uint32_t T = a.tile, tiles = (a.n + T - 1) / T;
+        hipLaunchKernelGGL(merge_gather_kernel, dim3((a.n + WG - 1) / WG), dim3(WG), 0, s, a);
+        hipLaunchKernelGGL(merge_sort_kernel, dim3(tiles), dim3(WG), T * (sizeof(Entry) + 8), s, a);
+        Entry *in = a.e0, *out = a.e1;
+        for (uint64_t run = T; run < a.n; run *= 2) {
+            hipLaunchKernelGGL(merge_pass_kernel, dim3(tiles), dim3(WG), T * sizeof(Entry), s, a, in, out,
+                               (uint32_t)run);
+            Entry *t = in;
+            in = out;
+            out = t;
+        }
+        a.sorted = in;
+        hipLaunchKernelGGL(merge_flag_kernel, dim3(a.nblocks), dim3(WG), 0, s, a);
+    }
+    hipLaunchKernelGGL(merge_scan_kernel, dim3(1), dim3(WG), 0, s, a);
+    if (a.n && a.cap)
+        hipLaunchKernelGGL(merge_scatter_kernel, dim3(a.nblocks), dim3(WG), 0, s, a);
+    return hipGetLastError() == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+}
+
+} /* namespace */
+
+extern "C" {
+
+size_t zscrc_device_merge_scratch_bytes(size_t n_total, const zscrc_merge_opts *opts)
+{
+    if (!tile_of(opts) || n_total > N_MAX)
+        return 0;
+    return plan_of(n_total).bytes;
+}
+
+int zscrc_device_merge(const void *d_src, uint64_t src_size, const zscrc_merge_list *lists, size_t k,
+                       struct zscrc_zs_record *d_out, size_t cap, uint64_t *d_res, void *scratch,
+                       const zscrc_merge_opts *opts, unsigned flags, void *stream)
+{
+    const uint32_t tile = tile_of(opts);
+    if (!d_res || (k && !lists) || (!d_src && src_size) || (cap && !d_out) ||
+        (reinterpret_cast<uintptr_t>(scratch) & 15) || (flags & ~ZSCRC_MERGE_DROP_DELETES) || !tile ||
+        k > ZSCRC_WALK_MULTI_MAX || src_size > zspack::SRC_MAX)
+        return ZSCRC_EINVAL;
+    uint64_t n = 0, filled = 0;
+    for (size_t l = 0; l < k; ++l) {
+        if (lists[l].n && !lists[l].d_recs)
+            return ZSCRC_EINVAL;
+        if (lists[l].n > N_MAX - n)
+            return ZSCRC_EINVAL;
+        n += lists[l].n;
+        filled += lists[l].n != 0;
+    }
+    Merge a{};
+    a.src = static_cast<const uint8_t *>(d_src);
+    a.src_size = src_size;
+    a.k = (uint32_t)filled;
+    a.n = (uint32_t)n;
+    a.tile = tile;
+    a.drop = flags & ZSCRC_MERGE_DROP_DELETES;
+    a.out = d_out;
+    a.cap = cap;
+    a.res = d_res;
+    const Plan p = plan_of(n);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    zs::Scratch *sc = zs::device_scratch();
+    if (!sc)
+        return ZSCRC_ENODEV;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (scratch)
+        return launch(a, p, scratch, *sc, lists, k, s);
+    const int arc = zs::scratch_acquire(*sc, p.bytes, s);
+    if (arc)
+        return arc;
+    return zs::scratch_done(*sc, s, launch(a, p, sc->p, *sc, lists, k, s));
+}
+
+} /* extern "C" */

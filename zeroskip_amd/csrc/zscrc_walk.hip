@@ -1163,6 +1163,38 @@ int scratch_done(Scratch &sc, hipStream_t s, int rc)
     return rc;
 }
 
+int stage_begin(Scratch &sc, size_t bytes)
+{
+    /* the staging's last copy must have run before its bytes change */
+    if (sc.staged_valid && hipEventSynchronize(sc.staged) != hipSuccess)
+        return ZSCRC_EHIP;
+    sc.staged_valid = false;
+    if (sc.pin_bytes < bytes) {
+        if (sc.pin)
+            (void)hipHostFree(sc.pin);
+        sc.pin = nullptr;
+        sc.pin_bytes = 0;
+        if (hipHostMalloc(&sc.pin, bytes, hipHostMallocDefault) != hipSuccess) {
+            sc.pin = nullptr;
+            return ZSCRC_ENOMEM;
+        }
+        sc.pin_bytes = bytes;
+    }
+    return ZSCRC_OK;
+}
+
+int stage_copy(Scratch &sc, void *d_dst, size_t bytes, hipStream_t s)
+{
+    if (hipMemcpyAsync(d_dst, sc.pin, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+        return ZSCRC_EHIP;
+    if (!sc.staged && hipEventCreateWithFlags(&sc.staged, hipEventDisableTiming) != hipSuccess)
+        sc.staged = nullptr;
+    sc.staged_valid = sc.staged && hipEventRecord(sc.staged, s) == hipSuccess;
+    if (!sc.staged_valid) /* no event to wait for before the next fill: drain instead */
+        return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+    return ZSCRC_OK;
+}
+
 } /* namespace zs */
 
 namespace {
@@ -1275,32 +1307,13 @@ int stage_descriptors(Scratch &sc, const zscrc_walk_image *images, size_t k, con
                       void *d_desc, hipStream_t s)
 {
     const size_t bytes = (k + 1) * sizeof(ImgD);
-    /* the staging's last copy must have run before its bytes change */
-    if (sc.staged_valid && hipEventSynchronize(sc.staged) != hipSuccess)
-        return ZSCRC_EHIP;
-    sc.staged_valid = false;
-    if (sc.pin_bytes < bytes) {
-        if (sc.pin)
-            (void)hipHostFree(sc.pin);
-        sc.pin = nullptr;
-        sc.pin_bytes = 0;
-        if (hipHostMalloc(&sc.pin, bytes, hipHostMallocDefault) != hipSuccess) {
-            sc.pin = nullptr;
-            return ZSCRC_ENOMEM;
-        }
-        sc.pin_bytes = bytes;
-    }
+    const int rc = zs::stage_begin(sc, bytes);
+    if (rc)
+        return rc;
     Plan p;
     if (!plan_multi(images, k, false, 0, o, &p, static_cast<ImgD *>(sc.pin)))
         return ZSCRC_EINVAL;
-    if (hipMemcpyAsync(d_desc, sc.pin, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-        return ZSCRC_EHIP;
-    if (!sc.staged && hipEventCreateWithFlags(&sc.staged, hipEventDisableTiming) != hipSuccess)
-        sc.staged = nullptr;
-    sc.staged_valid = sc.staged && hipEventRecord(sc.staged, s) == hipSuccess;
-    if (!sc.staged_valid) /* no event to wait for before the next fill: drain instead */
-        return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
-    return ZSCRC_OK;
+    return zs::stage_copy(sc, d_desc, bytes, s);
 }
 
 int launch_multi(const MWalk &m, hipStream_t s)

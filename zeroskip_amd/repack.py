@@ -212,6 +212,116 @@ def device_pack(d_src, recs, uuid: bytes, startidx: int = 0, endidx: int = 0, ou
     return out, res
 
 
+class MergeList(ctypes.Structure):
+    """zscrc_merge_list (include/zscrc.h)."""
+    _fields_ = [("d_recs", ctypes.c_void_p), ("n", ctypes.c_uint64), ("base", ctypes.c_uint64)]
+
+
+class MergeOpts(ctypes.Structure):
+    """zscrc_merge_opts (include/zscrc.h); 0 = the default."""
+    _fields_ = [("tile_records", ctypes.c_uint32)]
+
+
+MERGE_RES_WORDS = 8  # ZSCRC_MERGE_RES_WORDS
+MERGE_DROP_DELETES = 1  # ZSCRC_MERGE_DROP_DELETES
+
+
+def device_merge_scratch_bytes(n_total: int, tile_records: int = 0) -> int:
+    """zscrc_device_merge_scratch_bytes; 0 = a bad option or too many records."""
+    return lib().zscrc_device_merge_scratch_bytes(n_total, ctypes.byref(MergeOpts(tile_records)))
+
+
+def device_merge(d_src, lists, drop_deletes: bool = False, out=None, tile_records: int = 0, scratch=None):
+    """Device-resident record lists merged by key on the GPU
+    (zscrc_device_merge): (recs, res).  d_src: the uint8 device tensor the
+    rebased offsets point into; lists: a sequence of (recs, base), recs an
+    int64 [n, 4] device tensor such as zsfile.device_records returns, sliced
+    to its count, base added to its offsets.  A later record of a key wins
+    (later in its list, or in a later list); drop_deletes: a winning delete is
+    dropped instead of kept.  recs: the winners in key order, rebased, a list
+    device_pack takes over the same d_src.  res: int64 device tensor [code (0,
+    3 more winners than `out` holds, -1 a record outside d_src), winners or
+    the first bad sequence number, records in, deletes kept, sum of key
+    lengths, sum of value lengths, records superseded, deletes dropped].
+    out=None: a sizing call, one read of res[1] (the wrapper's only
+    synchronisation) and an output of exactly that size; recs is None when a
+    record is bad.  out given (an int64 [cap, 4] device tensor): one
+    asynchronous call on the current stream, recs = out (res[1] rows of it
+    are the list when res[0] == 0).  scratch: a 16-byte aligned uint8 tensor
+    of device_merge_scratch_bytes(n_total) bytes (default: the library's own)."""
+    import torch
+
+    dev = d_src.device
+    lists = list(lists)
+    arr = (MergeList * max(len(lists), 1))()
+    for j, (recs, base) in enumerate(lists):
+        n = int(recs.shape[0])
+        assert recs.dtype == torch.int64 and recs.is_contiguous() and (n == 0 or recs.shape[1] == 4)
+        arr[j].d_recs, arr[j].n, arr[j].base = (recs.data_ptr() if n else None), n, base
+    res = torch.empty(MERGE_RES_WORDS, dtype=torch.int64, device=dev)
+    opts = MergeOpts(tile_records)
+    src_bytes = d_src.numel() * d_src.element_size()
+
+    def call(o):
+        cap = 0 if o is None else o.numel() // 4
+        with torch.cuda.device(dev):
+            check(lib().zscrc_device_merge(
+                d_src.data_ptr() if src_bytes else None, src_bytes, arr, len(lists),
+                o.data_ptr() if cap else None, cap, res.data_ptr(),
+                None if scratch is None else scratch.data_ptr(), ctypes.byref(opts),
+                MERGE_DROP_DELETES if drop_deletes else 0, torch.cuda.current_stream(dev).cuda_stream),
+                "zscrc_device_merge")
+
+    if out is not None:
+        call(out)
+        return out, res
+    call(None)
+    code, n_out = (int(v) for v in res[:2].cpu())
+    if code < 0:
+        return None, res
+    out = torch.empty((n_out, 4), dtype=torch.int64, device=dev)
+    if n_out:
+        call(out)
+    return out, res
+
+
+def device_repack(d_arena, images, kinds, uuid: bytes, startidx: int, endidx: int, drop_deletes: bool):
+    """A repack of device-resident file images without an image byte or a key
+    crossing PCIe: zsfile.device_records per image, device_merge,
+    device_pack -> (file, report).  images: (offset, size) pairs into the
+    uint8 device tensor d_arena in load order (branch 1 of zsdb_repack: the
+    finalised files oldest first, drop_deletes False; branch 2: the newer
+    packed file first and the older last, drop_deletes True); kinds: each
+    image's zsfile kind.  file: the packed file as a uint8 device tensor.
+    report: records_in, records_out, superseded, deletes_dropped, file_bytes
+    and pack (device_pack's result words as a list).  The host reads each
+    image's record count, the winners' count and the file's size."""
+    from . import zsfile
+
+    lists = []
+    for (off, size), kind in zip(images, kinds):
+        recs, res = zsfile.device_records(d_arena[off:off + size], kind)
+        code, n = (int(v) for v in res[:2].cpu())
+        if code not in (0, zsfile.END):
+            raise ValueError("image at %d does not list: code %d" % (off, code))
+        lists.append((recs[:n], off))
+    import torch
+
+    # room for every record in: one merge, no sizing call
+    n_in = sum(int(r.shape[0]) for r, _ in lists)
+    merged, mres = device_merge(d_arena, lists, drop_deletes=drop_deletes,
+                                out=torch.empty((n_in, 4), dtype=torch.int64, device=d_arena.device))
+    m = [int(v) for v in mres.cpu()]
+    if m[0] != 0:
+        raise ValueError("record %d lies outside the arena" % m[1])
+    image, pres = device_pack(d_arena, merged[:m[1]], uuid, startidx, endidx)
+    p = [int(v) for v in pres.cpu()]
+    if image is None:
+        raise ValueError("record %d lies outside the arena" % p[1])
+    return image, {"records_in": m[2], "records_out": m[1], "superseded": m[6], "deletes_dropped": m[7],
+                   "file_bytes": p[2], "pack": p}
+
+
 def records(image, kind: int):
     """(key_off, key_len, val_off, val_len) uint64 arrays of a file image's
     records (zscrc_zs_records); val_off == 2**64-1 marks a delete."""
