@@ -253,6 +253,39 @@ def test_two_runs_bit_for_bit(gpu, cases):
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
 
 
+# ------------------------------------------------- more blocks than one scan chunk
+def test_more_blocks_than_one_scan_chunk(gpu):
+    """1024 * 1024 + 1 records are 1,025 blocks of 1,024 entries: merge_scan_kernel takes a second chunk of
+    block counts and merge_scatter_kernel's last block starts at a carried offset.  Record i is the 8-byte
+    big-endian key i // 2 with an empty value: every key twice (the later record wins), the last one once."""
+    n = 1024 * 1024 + 1
+    n_out = n // 2 + 1
+    src = (np.arange(n, dtype=np.uint64) // 2).astype(">u8").view(np.uint8)
+    recs = np.zeros((n, 4), np.uint64)
+    recs[:, 0] = 8 * np.arange(n, dtype=np.uint64)
+    recs[:, 1] = 8
+    recs[:, 2] = recs[:, 0] + 8
+    wres = [0, n_out, n, 0, 8 * n_out, 0, n - n_out, 0]
+    assert wres == [0, 524289, 1048577, 0, 8 * 524289, 0, 524288, 0]
+    d_src = torch.from_numpy(src).to(gpu)
+    perm = np.random.default_rng(5).permutation(n)
+    for order in (np.arange(n), perm):
+        listed = recs[order]
+        # sorted by (key, position in the list): the winner of a key is the last of its run
+        key = order // 2
+        by_key = np.lexsort((np.arange(n), key))
+        last = np.ones(n, bool)
+        last[:-1] = key[by_key][1:] != key[by_key][:-1]
+        want = listed[by_key[last]]
+        assert len(want) == n_out
+        if order is not perm:                                  # as listed: the odd i and the last record
+            assert np.array_equal(want, recs[np.r_[1:n:2, n - 1]])
+        out, res = repack.device_merge(d_src, [(_dev_recs(listed, gpu), 0)],
+                                       out=torch.zeros((n, 4), dtype=torch.int64, device=gpu))
+        assert [int(v) for v in res.cpu().numpy().view(np.uint64)] == wres
+        assert np.array_equal(out.cpu().numpy().view(np.uint64)[:n_out], want)
+
+
 # ------------------------------------------------------------------------ random
 @pytest.mark.parametrize("seed", range(20))
 def test_random(gpu, seed):

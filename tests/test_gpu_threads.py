@@ -5,7 +5,7 @@ The library's per-device state is shared by every caller: the class lists and
 part registers of variable batches, the span scratch, qteam_dyn's part
 registers, the verdict counter pairs, nbv's part registers, the walk's
 scratch, the host-batch staging and the scalar offload's cached stream
-(zscrc_api.cpp DevCtx, zscrc_walk.hip Scratch).  Calls that use it are
+(zscrc_api.cpp DevCtx, zscrc_scratch.cpp Scratch).  Calls that use it are
 enqueued under a lock and ordered across streams by an event; the code that
 decides whether two calls are on one stream compares stream handles -- and
 hipStreamPerThread is ONE handle for a different stream in every thread.

@@ -30,7 +30,7 @@ PKG = os.path.join(ROOT, "zeroskip_amd")
 HIPCC = "/opt/rocm/bin/hipcc"
 CLANG = "/opt/rocm/llvm/bin/clang"
 HOST_OBJS = ["zscrc_api", "zscrc_zs", "zscrc_consistent", "zscrc_gf2", "zscrc_cpu", "zscrc_pack", "zscrc_files",
-             "zscrc_repack", "zscrc_cpass", "zscrc_fill"]
+             "zscrc_repack", "zscrc_cpass", "zscrc_fill", "zscrc_scratch"]
 KERNEL_OBJS = ["zscrc_kernels", "zscrc_walk"]
 # the driver makes no device call; this keeps the process off every GPU whatever it links
 NO_GPU = {"ZSCRC_GPU_MIN": "0", "HIP_VISIBLE_DEVICES": "-1", "ROCR_VISIBLE_DEVICES": "-1"}

@@ -33,24 +33,25 @@
  * count and the output's capacity, the kernels read the totals the scan left
  * on the device.  A result code other than 0 makes every later kernel return
  * at once, and the span descriptors empty.
+ *
+ * The sums and prefix sums are zscrc_wg.h's with an addition that saturates
+ * (pack_scan_kernel: scan_counts); the scratch of a call comes through
+ * zs::with_scratch (zscrc_internal.h, zscrc_scratch.cpp).
  */
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
 
 #include "../../include/zscrc.h"
 #include "zscrc_internal.h"
 #include "zscrc_pack_layout.h"
+#include "zscrc_wg.h"
 
 namespace {
 
 using namespace zspack;
+using namespace zsdev;
 
-constexpr int WG = 256;
-constexpr uint32_t PER = 4;                       /* records a thread of a block */
-constexpr uint32_t BLOCK_RECS = WG * PER;
-constexpr uint64_t N_MAX = (1ull << 31) - 1;      /* records of one call */
 constexpr uint64_t DEF_TILE = 65536, TILE_MIN = 64, TILE_MAX = 65536;
 /* starts of a tile's records in LDS: the most records that reach into a tile
  * (24 bytes each at least), one more for the end, rounded up to whole rounds
@@ -80,42 +81,10 @@ struct Pack {
     uint64_t tile;
 };
 
-__device__ inline uint64_t wave_sum_sat(uint64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v = sat_add(v, __shfl_down(v, d, 64));
-    return v;
-}
-
-/* Exclusive saturating prefix sum of one value a thread over the workgroup;
- * total = the sum of all.  s: WG / 64 words of LDS, free again on return. */
-__device__ inline uint64_t wg_scan_sat(uint64_t *s, uint64_t mine, uint64_t &total)
-{
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(inc, d, 64);
-        if (lane >= (unsigned)d)
-            inc = sat_add(inc, o);
-    }
-    if (lane == 63)
-        s[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (unsigned w = 0; w < WG / 64; ++w) {
-        if (w < wave)
-            before = sat_add(before, s[w]);
-        all = sat_add(all, s[w]);
-    }
-    __syncthreads();
-    total = all;
-    /* exclusive: what lies before this thread; saturated sums stay saturated */
-    const uint64_t upto = sat_add(before, inc);
-    return upto == U64_MAX ? U64_MAX : upto - mine;
-}
+/* Sums of lengths saturate (zscrc_pack_layout.h): the addition of the scans. */
+struct SatAdd {
+    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return sat_add(a, b); }
+};
 
 /* The serialised length of record i, 0 past the list or for a bad record. */
 __device__ inline uint64_t len_of(const Pack &a, uint64_t i, bool *bad)
@@ -146,41 +115,17 @@ __global__ __launch_bounds__(WG) void pack_size_kernel(Pack a)
     }
     if (bad_at != U64_MAX)
         atomicMin(reinterpret_cast<unsigned long long *>(a.sc + SC_BAD), (unsigned long long)bad_at);
-    sum = wave_sum_sat(sum);
-    if ((threadIdx.x & 63) == 0)
-        s_part[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t t = 0;
-        for (unsigned w = 0; w < WG / 64; ++w)
-            t = sat_add(t, s_part[w]);
-        a.bsum[blockIdx.x] = t;
-    }
+    sum = wg_sum(s_part, sum, SatAdd{});
+    if (threadIdx.x == 0)
+        a.bsum[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(WG) void pack_scan_kernel(Pack a)
 {
     __shared__ uint64_t s_scan[WG / 64];
-    const uint64_t chunk = (uint64_t)WG * PER;
-    uint64_t carry = 0;
-    for (uint64_t c = 0; c < a.nblocks; c += chunk) {
-        const uint64_t first = c + (uint64_t)threadIdx.x * PER;
-        uint64_t v[PER], mine = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            v[k] = first + k < a.nblocks ? a.bsum[first + k] : 0;
-            mine = sat_add(mine, v[k]);
-        }
-        uint64_t total;
-        uint64_t at = sat_add(carry, wg_scan_sat(s_scan, mine, total));
-#pragma unroll
-        for (uint32_t k = 0; k < PER; ++k) {
-            if (first + k < a.nblocks)
-                a.bsum[first + k] = at;
-            at = sat_add(at, v[k]);
-        }
-        carry = sat_add(carry, total);
-    }
+    const uint64_t carry = scan_counts(
+        s_scan, a.nblocks, [&a](uint64_t i) { return a.bsum[i]; }, [&a](uint64_t i, uint64_t at) { a.bsum[i] = at; },
+        SatAdd{});
     if (threadIdx.x != 0)
         return;
     const uint64_t bad = a.n ? a.sc[SC_BAD] : U64_MAX;
@@ -223,7 +168,7 @@ __global__ __launch_bounds__(WG) void pack_prefix_kernel(Pack a)
         bool bad;
         const uint64_t len = len_of(a, i, &bad);
         uint64_t total;
-        const uint64_t at = carry + wg_scan_sat(s_scan, len, total);
+        const uint64_t at = carry + wg_scan(s_scan, len, total, SatAdd{});
         if (i < a.n) {
             a.start[i] = at;
             ptrs[i] = mem_be64(HDR + at);
@@ -336,8 +281,6 @@ __global__ __launch_bounds__(64) void pack_seal_kernel(Pack a, Header h)
     a.res[7] = final_crc;
 }
 
-bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
-
 /* The tile of a call; 0 = a bad option. */
 uint64_t tile_of(const zscrc_pack_opts *o)
 {
@@ -349,7 +292,7 @@ uint64_t blocks_of(uint64_t n) { return (n + BLOCK_RECS - 1) / BLOCK_RECS; }
 
 size_t scratch_need(uint64_t n)
 {
-    return (size_t)(((SC_WORDS + blocks_of(n) + 1 + n + 1) * 8 + 15) & ~15ull);
+    return up16((size_t)((SC_WORDS + blocks_of(n) + 1 + n + 1) * 8));
 }
 
 int launch(Pack &a, void *scratch, const Header &h, hipStream_t s)
@@ -436,16 +379,8 @@ int zscrc_device_pack(const void *d_src, uint64_t src_size, const struct zscrc_z
     a.tile = tile;
     const Header h = header_words(uuid, startidx, endidx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (scratch)
-        return launch(a, scratch, h, s);
-    zs::Scratch *sc = zs::device_scratch();
-    if (!sc)
-        return ZSCRC_ENODEV;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    const int arc = zs::scratch_acquire(*sc, scratch_need(n), s);
-    if (arc)
-        return arc;
-    return zs::scratch_done(*sc, s, launch(a, sc->p, h, s));
+    return zs::with_scratch(scratch, scratch_need(n), false, s,
+                            [&](void *p, zs::Scratch *) { return launch(a, p, h, s); });
 }
 
 } /* extern "C" */

@@ -8,6 +8,8 @@
 
 #include <mutex>
 
+#include "../../include/zscrc.h"
+
 /* Global operator-table block (uint32 words), built on the host per device. */
 enum {
     GT_S4 = 0,       /* shift(b<<8j, 4): slice-by-4 tables, j = byte position */
@@ -36,9 +38,9 @@ inline bool same_stream(hipStream_t a, hipStream_t b)
     return a == b && a != hipStreamPerThread;
 }
 
-/* The walk's library-owned scratch (zscrc_walk.hip), one buffer per device,
- * shared by every call there that passes no scratch of its own
- * (zscrc_device_walk, _records, _walk_multi, zscrc_device_pack): a call on
+/* The library-owned scratch of the device stages (zscrc_scratch.cpp), one
+ * buffer per device, shared by every call there that passes no scratch of its
+ * own (zscrc_device_walk, _records, _walk_multi, _pack, _merge): a call on
  * another stream than the last user's waits for that user's work. */
 struct Scratch {
     std::mutex mu;
@@ -47,8 +49,9 @@ struct Scratch {
     hipEvent_t last = nullptr;
     hipStream_t last_stream = nullptr;
     bool last_valid = false;
-    /* zscrc_device_walk_multi: pinned staging of the image descriptors on
-     * their way to the device, reused once its last copy has run (staged) */
+    /* zscrc_device_walk_multi, zscrc_device_merge: pinned staging of the image
+     * or list descriptors on their way to the device, reused once its last
+     * copy has run (staged) */
     void *pin = nullptr;
     size_t pin_bytes = 0;
     hipEvent_t staged = nullptr;
@@ -68,6 +71,27 @@ int stage_begin(Scratch &sc, size_t bytes);
 /* With sc.mu held: the staging's first `bytes` copied to d_dst (device) in
  * stream order. */
 int stage_copy(Scratch &sc, void *d_dst, size_t bytes, hipStream_t s);
+
+/* f(p, sc) with the scratch of a call: p = the caller's (own) or, own == NULL,
+ * the library's grown to `need` bytes, ordered after its last user before f
+ * and for its next one after.  sc = the device's Scratch with sc->mu held, or
+ * NULL: a call with a scratch of its own that needs no staging touches neither
+ * the device's Scratch nor its lock.  staging: f uses stage_begin / stage_copy,
+ * so the lock is held around f with the caller's scratch too. */
+template <class F>
+int with_scratch(void *own, size_t need, bool staging, hipStream_t s, F f)
+{
+    if (own && !staging)
+        return f(own, static_cast<Scratch *>(nullptr));
+    Scratch *sc = device_scratch();
+    if (!sc)
+        return ZSCRC_ENODEV;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (own)
+        return f(own, sc);
+    const int rc = scratch_acquire(*sc, need, s);
+    return rc ? rc : scratch_done(*sc, s, f(sc->p, sc));
+}
 
 struct RecDesc;
 
@@ -453,5 +477,20 @@ struct SpanFolds {
 };
 
 } /* namespace zs */
+
+/* What the device stages (zscrc_walk.hip, zscrc_devpack.hip, zscrc_merge.hip)
+ * share on host and device; their workgroup primitives: zscrc_wg.h. */
+namespace zsdev {
+
+constexpr int WG = 256;
+/* the packer and the merge cut a record list into blocks, one workgroup each */
+constexpr uint32_t PER = 4;                  /* records a thread of a block */
+constexpr uint32_t BLOCK_RECS = WG * PER;
+constexpr uint64_t N_MAX = (1ull << 31) - 1; /* records of one call */
+
+constexpr bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
+constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+} /* namespace zsdev */
 
 #endif

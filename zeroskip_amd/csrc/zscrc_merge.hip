@@ -30,26 +30,27 @@
  *
  * Every grid and the number of passes come from n_total on the host.  A bad
  * record makes every launch after the gather return at once.
+ *
+ * The sums and prefix sums are zscrc_wg.h's (merge_scan_kernel: scan_counts);
+ * the scratch of a call and the pinned staging of the list descriptors come
+ * through zs::with_scratch (zscrc_internal.h, zscrc_scratch.cpp).
  */
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 
 #include "../../include/zscrc.h"
 #include "zscrc_internal.h"
 #include "zscrc_merge_order.h"
+#include "zscrc_wg.h"
 
 namespace {
 
 using namespace zsmerge;
+using namespace zsdev;
 using zspack::U64_MAX;
 
-constexpr int WG = 256;
-constexpr uint32_t PER = 4;                       /* entries a thread of a block */
-constexpr uint32_t BLOCK_RECS = WG * PER;
-constexpr uint64_t N_MAX = (1ull << 31) - 1;      /* records of one call */
 /* the default: measured, DESIGN.md 2.6 (sorted input is 5 % slower than at
  * 1,024, shuffled input 21 % faster) */
 constexpr uint32_t DEF_TILE = 2048, TILE_MIN = 64, TILE_MAX = 2048;
@@ -197,51 +198,6 @@ __global__ __launch_bounds__(WG) void merge_pass_kernel(Merge a, const Entry *in
     }
 }
 
-/* Sum of one value a thread over the workgroup, in every thread.  s: WG / 64
- * words of LDS, free again on return. */
-__device__ inline uint64_t wg_sum(uint64_t *s, uint64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v += __shfl_xor(v, d, 64);
-    if ((threadIdx.x & 63) == 0)
-        s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint64_t all = 0;
-#pragma unroll
-    for (unsigned w = 0; w < WG / 64; ++w)
-        all += s[w];
-    __syncthreads();
-    return all;
-}
-
-/* Exclusive prefix sum of one value a thread over the workgroup; total = the
- * sum of all.  s as for wg_sum. */
-__device__ inline uint64_t wg_scan(uint64_t *s, uint64_t mine, uint64_t &total)
-{
-    const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t inc = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(inc, d, 64);
-        if (lane >= (unsigned)d)
-            inc += o;
-    }
-    if (lane == 63)
-        s[wave] = inc;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-#pragma unroll
-    for (unsigned w = 0; w < WG / 64; ++w) {
-        if (w < wave)
-            before += s[w];
-        all += s[w];
-    }
-    __syncthreads();
-    total = all;
-    return before + inc - mine;
-}
-
 __global__ __launch_bounds__(WG) void merge_flag_kernel(Merge a)
 {
     __shared__ uint64_t s_part[WG / 64];
@@ -292,26 +248,10 @@ __global__ __launch_bounds__(WG) void merge_scan_kernel(Merge a)
     __shared__ uint64_t s_scan[WG / 64];
     const uint64_t bad = a.n ? a.sc[SC_BAD] : U64_MAX;
     uint64_t carry = 0;
-    if (bad == U64_MAX) {
-        for (uint64_t c = 0; c < a.nblocks; c += BLOCK_RECS) {
-            const uint64_t first = c + (uint64_t)threadIdx.x * PER;
-            uint64_t v[PER], mine = 0;
-#pragma unroll
-            for (uint32_t k = 0; k < PER; ++k) {
-                v[k] = first + k < a.nblocks ? a.bcount[first + k] : 0;
-                mine += v[k];
-            }
-            uint64_t total;
-            uint64_t at = carry + wg_scan(s_scan, mine, total);
-#pragma unroll
-            for (uint32_t k = 0; k < PER; ++k) {
-                if (first + k < a.nblocks)
-                    a.bcount[first + k] = (uint32_t)at;
-                at += v[k];
-            }
-            carry += total;
-        }
-    }
+    if (bad == U64_MAX)
+        carry = scan_counts(
+            s_scan, a.nblocks, [&a](uint64_t i) { return (uint64_t)a.bcount[i]; },
+            [&a](uint64_t i, uint64_t at) { a.bcount[i] = (uint32_t)at; });
     if (threadIdx.x != 0)
         return;
     if (bad != U64_MAX) {
@@ -358,10 +298,8 @@ __global__ __launch_bounds__(WG) void merge_scatter_kernel(Merge a)
 uint32_t tile_of(const zscrc_merge_opts *o)
 {
     const uint32_t t = o && o->tile_records ? o->tile_records : DEF_TILE;
-    return (t & (t - 1)) == 0 && t >= TILE_MIN && t <= TILE_MAX ? t : 0;
+    return pow2(t) && t >= TILE_MIN && t <= TILE_MAX ? t : 0;
 }
-
-constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 /* The pieces of the scratch for n records: the words, the descriptors of at
  * most min(n, ZSCRC_WALK_MULTI_MAX) lists that are not empty and the entry
@@ -482,16 +420,8 @@ int zscrc_device_merge(const void *d_src, uint64_t src_size, const zscrc_merge_l
     a.res = d_res;
     const Plan p = plan_of(n);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    zs::Scratch *sc = zs::device_scratch();
-    if (!sc)
-        return ZSCRC_ENODEV;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    if (scratch)
-        return launch(a, p, scratch, *sc, lists, k, s);
-    const int arc = zs::scratch_acquire(*sc, p.bytes, s);
-    if (arc)
-        return arc;
-    return zs::scratch_done(*sc, s, launch(a, p, sc->p, *sc, lists, k, s));
+    return zs::with_scratch(scratch, p.bytes, true, s,
+                            [&](void *sp, zs::Scratch *sc) { return launch(a, p, sp, *sc, lists, k, s); });
 }
 
 } /* extern "C" */

@@ -24,14 +24,14 @@
 
 namespace zspack {
 
+using zsrec::HDR;
 using zsrec::rup8;
+using zsrec::U64_MAX;
 
-constexpr uint64_t HDR = 40;
 constexpr uint64_t MAX_SHORT_KEY_LEN = 65535;    /* zeroskip-priv.h */
 constexpr uint64_t MAX_SHORT_VAL_LEN = 16777215; /* zeroskip-priv.h:171 */
 constexpr uint64_t SIGNATURE = 0x5a45524f534b4950ull;
 constexpr uint32_t VERSION = 1;
-constexpr uint64_t U64_MAX = ~0ull;
 /* A source of more bytes is refused by the entry point: below it the length
  * of one valid record cannot wrap. */
 constexpr uint64_t SRC_MAX = 1ull << 62;

@@ -33,6 +33,7 @@ enum {
 };
 
 constexpr uint64_t HDR = 40;
+constexpr uint64_t U64_MAX = ~0ull;
 
 /* Big-endian 64-bit word at any byte address. */
 ZSREC_HD inline uint64_t be64(const uint8_t *p)

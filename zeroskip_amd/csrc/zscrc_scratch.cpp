@@ -1,0 +1,129 @@
+/*
+ * zscrc_scratch.cpp -- the library-owned scratch of the device stages
+ * (zs::Scratch, zscrc_internal.h): one buffer and one pinned staging per
+ * device, shared by every call there that passes no scratch of its own
+ * (zscrc_device_walk, _records, _walk_multi, _pack, _merge).  A call on another
+ * stream than the last user's waits for that user's work.  The calls reach it
+ * through zs::with_scratch (zscrc_internal.h).
+ */
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+
+#include "../../include/zscrc.h"
+#include "zscrc_internal.h"
+
+namespace {
+
+constexpr int MAX_DEV = 64;
+zs::Scratch g_scratch[MAX_DEV];
+
+} /* namespace */
+
+namespace zs {
+
+Scratch *device_scratch()
+{
+    int dev = -1;
+    return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_DEV ? &g_scratch[dev] : nullptr;
+}
+
+int scratch_acquire(Scratch &sc, size_t need, hipStream_t s)
+{
+    if (sc.bytes < need) {
+        if (sc.p)
+            (void)hipFree(sc.p); /* waits for the device: no user is left */
+        sc.p = nullptr;
+        sc.bytes = 0;
+        sc.last_valid = false;
+        /* about the image's size: no slack on top */
+        if (hipMalloc(&sc.p, need) != hipSuccess) {
+            sc.p = nullptr;
+            return ZSCRC_ENOMEM;
+        }
+        sc.bytes = need;
+    }
+    /* a wait on the stream's own event is harmless: "not certainly the same stream" waits */
+    if (sc.last_valid && !zs::same_stream(sc.last_stream, s) && hipStreamWaitEvent(s, sc.last, 0) != hipSuccess)
+        return ZSCRC_EHIP;
+    return ZSCRC_OK;
+}
+
+int scratch_done(Scratch &sc, hipStream_t s, int rc)
+{
+    if (!sc.last && hipEventCreateWithFlags(&sc.last, hipEventDisableTiming) != hipSuccess)
+        sc.last = nullptr;
+    sc.last_valid = sc.last && hipEventRecord(sc.last, s) == hipSuccess;
+    sc.last_stream = s;
+    if (!sc.last_valid && rc == ZSCRC_OK) /* no event to order the next user by: drain instead */
+        return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+    return rc;
+}
+
+int stage_begin(Scratch &sc, size_t bytes)
+{
+    /* the staging's last copy must have run before its bytes change */
+    if (sc.staged_valid && hipEventSynchronize(sc.staged) != hipSuccess)
+        return ZSCRC_EHIP;
+    sc.staged_valid = false;
+    if (sc.pin_bytes < bytes) {
+        if (sc.pin)
+            (void)hipHostFree(sc.pin);
+        sc.pin = nullptr;
+        sc.pin_bytes = 0;
+        if (hipHostMalloc(&sc.pin, bytes, hipHostMallocDefault) != hipSuccess) {
+            sc.pin = nullptr;
+            return ZSCRC_ENOMEM;
+        }
+        sc.pin_bytes = bytes;
+    }
+    return ZSCRC_OK;
+}
+
+int stage_copy(Scratch &sc, void *d_dst, size_t bytes, hipStream_t s)
+{
+    if (hipMemcpyAsync(d_dst, sc.pin, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+        return ZSCRC_EHIP;
+    if (!sc.staged && hipEventCreateWithFlags(&sc.staged, hipEventDisableTiming) != hipSuccess)
+        sc.staged = nullptr;
+    sc.staged_valid = sc.staged && hipEventRecord(sc.staged, s) == hipSuccess;
+    if (!sc.staged_valid) /* no event to wait for before the next fill: drain instead */
+        return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+    return ZSCRC_OK;
+}
+
+} /* namespace zs */
+
+/* zscrc_release_cache(): the scratch and the staging, every device. */
+extern "C" void zs_walk_release_cache(void)
+{
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    for (int d = 0; d < MAX_DEV; ++d) {
+        zs::Scratch &sc = g_scratch[d];
+        std::lock_guard<std::mutex> lk(sc.mu);
+        if (!sc.p && !sc.last && !sc.pin && !sc.staged)
+            continue;
+        (void)hipSetDevice(d);
+        if (sc.p)
+            (void)hipFree(sc.p);
+        if (sc.last)
+            (void)hipEventDestroy(sc.last);
+        if (sc.staged_valid)
+            (void)hipEventSynchronize(sc.staged);
+        if (sc.pin)
+            (void)hipHostFree(sc.pin);
+        if (sc.staged)
+            (void)hipEventDestroy(sc.staged);
+        sc.p = nullptr;
+        sc.bytes = 0;
+        sc.last = nullptr;
+        sc.last_valid = false;
+        sc.pin = nullptr;
+        sc.pin_bytes = 0;
+        sc.staged = nullptr;
+        sc.staged_valid = false;
+    }
+    if (cur >= 0)
+        (void)hipSetDevice(cur);
+}

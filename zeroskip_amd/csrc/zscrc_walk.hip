@@ -47,6 +47,12 @@
  * images (the lister never looks at a commit's span length, the walk never at
  * a key length), so neither can use the other's tables.  Packed images have no
  * chain: records_packed_*_kernel parse the pointer section one pointer a thread.
+ *
+ * Shared with the other device stages: the record words and types
+ * (zscrc_records.h), the many-image walk's scan of the counts (scan_counts,
+ * zscrc_wg.h; the emit sweep keeps a scan of its own, tile_scan) and the
+ * scratch of a call (zs::with_scratch, zscrc_internal.h; the library's buffer
+ * and its pinned staging: zscrc_scratch.cpp).
  */
 #include <hip/hip_runtime.h>
 
@@ -58,15 +64,14 @@
 #include "../../include/zscrc.h"
 #include "zscrc_internal.h"
 #include "zscrc_records.h"
+#include "zscrc_wg.h"
 
 namespace {
 
-using zs::device_scratch;
+using namespace zsdev;
+using namespace zsrec; /* be64, rup8, HDR, U64_MAX and the record types T_* */
 using zs::Scratch;
-using zs::scratch_acquire;
-using zs::scratch_done;
 
-constexpr int WG = 256;
 constexpr uint32_t TILE_SLOTS_MAX = 2048;            /* 16 KiB of image per tile */
 constexpr uint32_t SPT = TILE_SLOTS_MAX / WG;         /* a thread's slots of a tile: i = thread + j * WG */
 constexpr uint64_t DEF_BLOCK = 1ull << 20, DEF_TILE = 16384;
@@ -74,13 +79,7 @@ constexpr uint64_t BLOCK_MAX = 1ull << 30;
 constexpr uint64_t BLOCKS_MAX = (1ull << 24) - 1;     /* blocks of one image */
 constexpr uint32_t J_EXIT = 0x80000000u;              /* J: low bits = the exit record's slot in the block */
 constexpr uint32_t NONE = 0xFFFFFFFFu;
-constexpr uint64_t U64_MAX = ~0ull;
-constexpr uint64_t HDR = 40;
 
-enum {
-    T_KEY = 1, T_VALUE = 2, T_COMMIT = 4, T_FINAL = 16, T_DELETED = 64,
-    T_LONG_KEY = 33, T_LONG_COMMIT = 36, T_LONG_FINAL = 48, T_LONG_DELETED_ALIAS = 32,
-};
 /* What a step finds: S_OUT = a record the walk puts out (the commit walk: a
  * commit, S_COMMIT; the record lister: a key or delete record), S_ADV = one it
  * only advances over; the shared bodies look at nothing else of a kind. */
@@ -113,19 +112,6 @@ struct Walk {
     uint64_t cap;
     uint64_t *res;
 };
-
-/* Big-endian 64-bit word at any byte address. */
-__device__ __forceinline__ uint64_t be64(const uint8_t *p)
-{
-    if ((reinterpret_cast<uintptr_t>(p) & 7) == 0)
-        return __builtin_bswap64(*reinterpret_cast<const uint64_t *>(p));
-    uint64_t v = 0;
-    for (int i = 0; i < 8; ++i)
-        v = (v << 8) | p[i];
-    return v;
-}
-
-__device__ __forceinline__ uint64_t rup8(uint64_t n) { return (n + 7) & ~7ull; }
 
 /* The record word at off < size, 0 where fewer than 8 bytes are left. */
 __device__ __forceinline__ uint64_t word_at(const uint8_t *img, uint64_t size, uint64_t off)
@@ -164,7 +150,7 @@ __device__ Step step_w(const uint8_t *img, uint64_t size, uint64_t off, uint64_t
             return s;
         s.kind = S_ADV;
         s.next = v + 16 + rup8(vlen);
-    } else if (t == T_DELETED || t == T_LONG_DELETED_ALIAS) {
+    } else if (t == T_DELETED || t == T_LONG_DELETED) {
         if (room < 24)
             return s;
         const uint64_t klen = t == T_DELETED ? ((w >> 40) & 0xFFFF) : be64(img + off + 8);
@@ -239,10 +225,13 @@ __device__ __forceinline__ void tile_words(const Walk &a, uint64_t t0, uint64_t 
     }
 }
 
-/* Inclusive prefix sum over the workgroup's threads of one value each; total
- * = the last thread's.  The caller's next barrier comes before s changes. */
+/* The emit sweep's scan: inclusive prefix sum over the workgroup's threads of
+ * one value each, double-buffered in LDS; total = the last thread's.  The
+ * caller's next barrier comes before s changes.  (Every other scan is
+ * zscrc_wg.h's wg_scan; this one stays until a change to the hot emit kernels
+ * is measured on its own.) */
 template <class T>
-__device__ __forceinline__ T wg_scan(T (&s)[2][WG], T mine, T &total)
+__device__ __forceinline__ T tile_scan(T (&s)[2][WG], T mine, T &total)
 {
     int cur = 0;
     s[0][threadIdx.x] = mine;
@@ -755,7 +744,7 @@ __device__ __forceinline__ void emit_sweep(const Walk &a, uint32_t blk, uint64_t
             for (uint32_t j = 0; j < per; ++j)
                 mine += s_p[first + j];
         uint32_t total;
-        uint64_t rank = base + wg_scan(s_scan, mine, total) - mine;
+        uint64_t rank = base + tile_scan(s_scan, mine, total) - mine;
         if (mine) {
             for (uint32_t j = 0; j < per; ++j) {
                 if (!s_p[first + j])
@@ -909,7 +898,7 @@ __global__ __launch_bounds__(WG) void records_packed_emit_kernel(Packed a)
  *                            initial [3] [4]; past an unaligned next offset it
  *                            only counts (serial_loop)
  *   walk_multi_scan_kernel   one workgroup: row[6] = exclusive prefix sum of
- *                            the counts, chunk by chunk with a carry; totals
+ *                            the counts (scan_counts, zscrc_wg.h); totals
  *   walk_multi_emit_kernel   one workgroup per (image, block): emit_sweep from
  *                            row[6]; and one lane per image that walks a
  *                            counted tail again, storing its spans
@@ -935,7 +924,6 @@ struct MWalk {
     uint64_t *rows, *tot;
 };
 
-constexpr uint32_t SCAN_PER = 4;                /* the scan's counts per thread and chunk */
 constexpr uint64_t MULTI_MAX = ZSCRC_WALK_MULTI_MAX;
 constexpr int ROW = ZSCRC_WALK_ROW_WORDS;
 
@@ -1018,29 +1006,10 @@ __global__ __launch_bounds__(WG) void walk_multi_chain_kernel(MWalk a)
 
 __global__ __launch_bounds__(WG) void walk_multi_scan_kernel(MWalk a)
 {
-    __shared__ uint64_t s_scan[2][WG];
-    const uint32_t chunk = WG * SCAN_PER;
-    const uint32_t chunks = (a.k + chunk - 1) / chunk;
-    uint64_t carry = 0;
-    for (uint32_t c = 0; c < chunks; ++c) {
-        const uint64_t first = (uint64_t)c * chunk + threadIdx.x * SCAN_PER;
-        uint64_t cnt[SCAN_PER], mine = 0;
-#pragma unroll
-        for (uint32_t i = 0; i < SCAN_PER; ++i) {
-            cnt[i] = first + i < a.k ? a.rows[(first + i) * ROW + 1] : 0;
-            mine += cnt[i];
-        }
-        uint64_t total;
-        uint64_t at = carry + wg_scan(s_scan, mine, total) - mine;
-#pragma unroll
-        for (uint32_t i = 0; i < SCAN_PER; ++i) {
-            if (first + i < a.k)
-                a.rows[(first + i) * ROW + 6] = at;
-            at += cnt[i];
-        }
-        carry += total;
-        __syncthreads(); /* s_scan is rewritten by the next chunk */
-    }
+    __shared__ uint64_t s_scan[WG / 64];
+    const uint64_t carry = scan_counts(
+        s_scan, a.k, [&a](uint64_t i) { return a.rows[i * ROW + 1]; },
+        [&a](uint64_t i, uint64_t at) { a.rows[i * ROW + 6] = at; });
     if (threadIdx.x == 0) {
         a.tot[0] = carry > a.cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : 0;
         a.tot[1] = carry;
@@ -1088,8 +1057,6 @@ __global__ __launch_bounds__(WG) void walk_multi_headers_kernel(const uint8_t *a
 
 /* ------------------------------------------------------------------ host */
 
-bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
-
 /* The geometry for an image: false = bad options. */
 bool geometry(uint64_t size, const zscrc_walk_opts *o, Walk *w)
 {
@@ -1115,90 +1082,6 @@ bool serial_only(const Walk &w, unsigned flags) { return (flags & ZSCRC_WALK_SER
 
 size_t scratch_bytes(const Walk &w) { return (size_t)(w.nblocks * sizeof(Entry) + w.ns * 8); }
 
-/* Library-owned scratch (zs::Scratch, zscrc_internal.h), one buffer per device,
- * shared by every call there -- the device packer's (zscrc_devpack.hip) too: a
- * call on another stream than the last user's waits for that user's work. */
-constexpr int MAX_DEV = 64;
-Scratch g_scratch[MAX_DEV];
-
-} /* namespace */
-
-namespace zs {
-
-Scratch *device_scratch()
-{
-    int dev = -1;
-    return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAX_DEV ? &g_scratch[dev] : nullptr;
-}
-
-int scratch_acquire(Scratch &sc, size_t need, hipStream_t s)
-{
-    if (sc.bytes < need) {
-        if (sc.p)
-            (void)hipFree(sc.p); /* waits for the device: no user is left */
-        sc.p = nullptr;
-        sc.bytes = 0;
-        sc.last_valid = false;
-        /* about the image's size: no slack on top */
-        if (hipMalloc(&sc.p, need) != hipSuccess) {
-            sc.p = nullptr;
-            return ZSCRC_ENOMEM;
-        }
-        sc.bytes = need;
-    }
-    /* a wait on the stream's own event is harmless: "not certainly the same stream" waits */
-    if (sc.last_valid && !zs::same_stream(sc.last_stream, s) && hipStreamWaitEvent(s, sc.last, 0) != hipSuccess)
-        return ZSCRC_EHIP;
-    return ZSCRC_OK;
-}
-
-int scratch_done(Scratch &sc, hipStream_t s, int rc)
-{
-    if (!sc.last && hipEventCreateWithFlags(&sc.last, hipEventDisableTiming) != hipSuccess)
-        sc.last = nullptr;
-    sc.last_valid = sc.last && hipEventRecord(sc.last, s) == hipSuccess;
-    sc.last_stream = s;
-    if (!sc.last_valid && rc == ZSCRC_OK) /* no event to order the next user by: drain instead */
-        return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
-    return rc;
-}
-
-int stage_begin(Scratch &sc, size_t bytes)
-{
-    /* the staging's last copy must have run before its bytes change */
-    if (sc.staged_valid && hipEventSynchronize(sc.staged) != hipSuccess)
-        return ZSCRC_EHIP;
-    sc.staged_valid = false;
-    if (sc.pin_bytes < bytes) {
-        if (sc.pin)
-            (void)hipHostFree(sc.pin);
-        sc.pin = nullptr;
-        sc.pin_bytes = 0;
-        if (hipHostMalloc(&sc.pin, bytes, hipHostMallocDefault) != hipSuccess) {
-            sc.pin = nullptr;
-            return ZSCRC_ENOMEM;
-        }
-        sc.pin_bytes = bytes;
-    }
-    return ZSCRC_OK;
-}
-
-int stage_copy(Scratch &sc, void *d_dst, size_t bytes, hipStream_t s)
-{
-    if (hipMemcpyAsync(d_dst, sc.pin, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-        return ZSCRC_EHIP;
-    if (!sc.staged && hipEventCreateWithFlags(&sc.staged, hipEventDisableTiming) != hipSuccess)
-        sc.staged = nullptr;
-    sc.staged_valid = sc.staged && hipEventRecord(sc.staged, s) == hipSuccess;
-    if (!sc.staged_valid) /* no event to wait for before the next fill: drain instead */
-        return hipStreamSynchronize(s) == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
-    return ZSCRC_OK;
-}
-
-} /* namespace zs */
-
-namespace {
-
 /* records: the record lister's instances instead of the commit walk's. */
 int launch(const Walk &w, unsigned flags, hipStream_t s, bool records)
 {
@@ -1217,26 +1100,14 @@ int launch(const Walk &w, unsigned flags, hipStream_t s, bool records)
  * with the caller's scratch or, scratch == NULL, the library's. */
 int walk_single(Walk &w, void *scratch, unsigned flags, hipStream_t s, bool records)
 {
-    auto place = [&w](void *p) {
+    if (serial_only(w, flags)) /* touches no scratch */
+        return launch(w, flags, s, records);
+    return zs::with_scratch(scratch, scratch_bytes(w), false, s, [&](void *p, Scratch *) {
         w.entry = static_cast<Entry *>(p);
         w.J = reinterpret_cast<uint32_t *>(w.entry + w.nblocks);
         w.C = w.J + w.ns;
-    };
-    if (serial_only(w, flags)) /* touches no scratch */
         return launch(w, flags, s, records);
-    if (scratch) {
-        place(scratch);
-        return launch(w, flags, s, records);
-    }
-    Scratch *sc = device_scratch();
-    if (!sc)
-        return ZSCRC_ENODEV;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    const int arc = scratch_acquire(*sc, scratch_bytes(w), s);
-    if (arc)
-        return arc;
-    place(sc->p);
-    return scratch_done(*sc, s, launch(w, flags, s, records));
+    });
 }
 
 int launch_packed(const Packed &a, unsigned flags, hipStream_t s)
@@ -1294,7 +1165,7 @@ bool plan_multi(const zscrc_walk_image *images, size_t k, bool check_arena, uint
     p->nslots = slots;
     p->nblocks = blocks;
     p->tail_at = (k + 1) * sizeof(ImgD);
-    p->entry_at = p->tail_at + ((k * 8 + 15) & ~(size_t)15);
+    p->entry_at = p->tail_at + up16(k * 8);
     p->j_at = p->entry_at + (size_t)blocks * sizeof(Entry);
     p->c_at = p->j_at + (size_t)slots * 4;
     p->bytes = p->c_at + (size_t)slots * 4;
@@ -1387,17 +1258,10 @@ int zscrc_device_records(const void *d_image, uint64_t image_size, int kind, str
     }
     Packed a{static_cast<const uint8_t *>(d_image), image_size, reinterpret_cast<uint64_t *>(d_recs), cap, d_res,
              static_cast<uint64_t *>(scratch)};
-    if (scratch)
+    return zs::with_scratch(scratch, PK_WORDS * sizeof(uint64_t), false, s, [&](void *p, Scratch *) {
+        a.sc = static_cast<uint64_t *>(p);
         return launch_packed(a, flags, s);
-    Scratch *sc = device_scratch();
-    if (!sc)
-        return ZSCRC_ENODEV;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    const int arc = scratch_acquire(*sc, PK_WORDS * sizeof(uint64_t), s);
-    if (arc)
-        return arc;
-    a.sc = static_cast<uint64_t *>(sc->p);
-    return scratch_done(*sc, s, launch_packed(a, flags, s));
+    });
 }
 
 size_t zscrc_device_walk_multi_scratch_bytes(const zscrc_walk_image *images, size_t k, const zscrc_walk_opts *opts)
@@ -1416,23 +1280,8 @@ int zscrc_device_walk_multi(const void *d_arena, uint64_t arena_size, const zscr
         (reinterpret_cast<uintptr_t>(scratch) & 15) || !plan_multi(images, k, true, arena_size, opts, &p, nullptr))
         return ZSCRC_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    Scratch *sc = device_scratch();
-    if (!sc)
-        return ZSCRC_ENODEV;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    if (!scratch) {
-        const int arc = scratch_acquire(*sc, p.bytes, s);
-        if (arc)
-            return arc;
-    }
-    uint8_t *base = static_cast<uint8_t *>(scratch ? scratch : sc->p);
     MWalk m{};
     m.arena = static_cast<const uint8_t *>(d_arena);
-    m.im = reinterpret_cast<const ImgD *>(base);
-    m.tail_n = reinterpret_cast<uint64_t *>(base + p.tail_at);
-    m.entry = reinterpret_cast<Entry *>(base + p.entry_at);
-    m.J = reinterpret_cast<uint32_t *>(base + p.j_at);
-    m.C = reinterpret_cast<uint32_t *>(base + p.c_at);
     m.k = (uint32_t)k;
     m.nblocks = (uint32_t)p.nblocks;
     m.bs = p.bs;
@@ -1444,10 +1293,16 @@ int zscrc_device_walk_multi(const void *d_arena, uint64_t arena_size, const zscr
     m.cap = cap;
     m.rows = d_rows;
     m.tot = d_tot;
-    int rc = stage_descriptors(*sc, images, k, opts, base, s);
-    if (!rc)
-        rc = launch_multi(m, s);
-    return scratch ? rc : scratch_done(*sc, s, rc);
+    return zs::with_scratch(scratch, p.bytes, true, s, [&](void *sp, Scratch *sc) {
+        uint8_t *base = static_cast<uint8_t *>(sp);
+        m.im = reinterpret_cast<const ImgD *>(base);
+        m.tail_n = reinterpret_cast<uint64_t *>(base + p.tail_at);
+        m.entry = reinterpret_cast<Entry *>(base + p.entry_at);
+        m.J = reinterpret_cast<uint32_t *>(base + p.j_at);
+        m.C = reinterpret_cast<uint32_t *>(base + p.c_at);
+        const int rc = stage_descriptors(*sc, images, k, opts, base, s);
+        return rc ? rc : launch_multi(m, s);
+    });
 }
 
 int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size, const zscrc_walk_image *images, size_t k,
@@ -1458,7 +1313,7 @@ int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size, const z
         return ZSCRC_EINVAL;
     memset(reps, 0, k * sizeof *reps);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    Scratch *sc = device_scratch();
+    Scratch *sc = zs::device_scratch();
     if (!sc)
         return ZSCRC_ENODEV;
     /* device: descriptors, the rows, the totals, the gathered headers; host:
@@ -1561,40 +1416,6 @@ int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size, const z
     free(st);
     free(host);
     return rc;
-}
-
-/* zscrc_release_cache(): the walk's scratch and descriptor staging, every device. */
-void zs_walk_release_cache(void)
-{
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    for (int d = 0; d < MAX_DEV; ++d) {
-        Scratch &sc = g_scratch[d];
-        std::lock_guard<std::mutex> lk(sc.mu);
-        if (!sc.p && !sc.last && !sc.pin && !sc.staged)
-            continue;
-        (void)hipSetDevice(d);
-        if (sc.p)
-            (void)hipFree(sc.p);
-        if (sc.last)
-            (void)hipEventDestroy(sc.last);
-        if (sc.staged_valid)
-            (void)hipEventSynchronize(sc.staged);
-        if (sc.pin)
-            (void)hipHostFree(sc.pin);
-        if (sc.staged)
-            (void)hipEventDestroy(sc.staged);
-        sc.p = nullptr;
-        sc.bytes = 0;
-        sc.last = nullptr;
-        sc.last_valid = false;
-        sc.pin = nullptr;
-        sc.pin_bytes = 0;
-        sc.staged = nullptr;
-        sc.staged_valid = false;
-    }
-    if (cur >= 0)
-        (void)hipSetDevice(cur);
 }
 
 } /* extern "C" */
