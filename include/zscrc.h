@@ -616,6 +616,68 @@ int zscrc_device_records(const void *d_image, uint64_t image_size, int kind,
                          struct zscrc_zs_record *d_recs, size_t cap, uint64_t *d_res,
                          void *scratch, const zscrc_walk_opts *opts, unsigned flags, void *stream);
 
+/* zscrc_device_records over k ACTIVE / FINALISED images of one device buffer
+ * (the arena of zscrc_device_walk_multi) in one call and four launches
+ * whatever k is -- table, chain, scan, emit; no workgroup waits for another and
+ * nothing is copied to the host.  The first stage of a repack of a whole DB:
+ * its output is one record list over the arena.  Packed files have no chain
+ * and keep zscrc_device_records (as zscrc_device_verify_images leaves them to
+ * zscrc_device_verify_image). */
+#define ZSCRC_RECORDS_ROW_WORDS 12
+#define ZSCRC_RECORDS_TOT_WORDS 8
+/* Bytes of scratch zscrc_device_records_multi needs: the bound, the promises
+ * and the refusals of zscrc_device_walk_multi_scratch_bytes (at most the sum
+ * over the images of 8 * ceil(size / 8) + 16 * blocks, plus 64 * (k + 1);
+ * appending an image never shrinks it; 0 = bad arguments). */
+size_t zscrc_device_records_multi_scratch_bytes(const zscrc_walk_image *images, size_t k,
+                                                const zscrc_walk_opts *opts);
+/* Asynchronous on `stream`.  images: a HOST array of k descriptors, copied
+ * through the library's pinned staging exactly as zscrc_device_walk_multi
+ * copies its own; images may lie at any byte offset of the arena, in any order,
+ * overlap and repeat; one of fewer than 40 bytes (0 too) is legal and has no
+ * records.  Nothing outside [d_arena + off, + size) of an image is read for it.
+ * d_recs (device, cap entries of 32 bytes): the records of image 0 first, then
+ * image 1's ..., each image's in the lister's order.  An entry is what
+ * zscrc_zs_records writes for that image's bytes alone with images[j].off added
+ * to key_off, and to val_off unless that is ZSCRC_ZS_DELETED (which stays);
+ * key_len and val_len unchanged (no add can wrap: every image lies inside the
+ * arena).  The array is therefore ONE zscrc_merge_list with base 0 over
+ * d_arena, whose sequence numbers are those the merge gives the k separate
+ * lists, and a list zscrc_device_pack takes as it is.  Entries at index >= cap
+ * are not written (cap 0: d_recs may be NULL).  There is no per-record image
+ * array: row word [9] locates an image's records.
+ * d_rows (device, k * ZSCRC_RECORDS_ROW_WORDS words), row j, image-relative:
+ *   [0] zscrc_zs_records' code for image j alone with unlimited room (END /
+ *       STOPPED / TRUNCATED, never OVERFLOW);
+ *       (uint64_t)(int64_t)ZSCRC_EINVAL for size < 40
+ *   [1] .. [8] zscrc_device_records' result words [1] .. [8] for that image
+ *       alone: its records, the offset where the lister ended, the deletes,
+ *       the sum of key_len, the sum of val_len, the longest key, the longest
+ *       value, the offset where a one-lane loop took over or UINT64_MAX
+ *       (size < 40: [1] .. [7] 0, [8] UINT64_MAX)
+ *   [9] the index of its first record in the output: the exclusive prefix sum
+ *       of [1], also for images without records   [10] [11] 0
+ * d_tot (device, ZSCRC_RECORDS_TOT_WORDS words): [0] ZSCRC_ZS_OVERFLOW if there
+ * are more records than cap, else 0; [1] the records of all images, counted
+ * past cap too; [2] the deletes, [3] the sum of key_len, [4] the sum of val_len
+ * (sums modulo 2^64), [5] the longest key, [6] the longest value -- [1], [3]
+ * and [4] are what zscrc_device_pack_bound takes; [7] the images whose row [0]
+ * is not ZSCRC_ZS_END: one word tells that every image listed to its end.
+ * Sums and maxima are integer atomics only: the results do not depend on the
+ * order of the workgroups.
+ * flags must be 0.  scratch: 16-byte aligned device memory of
+ * zscrc_device_records_multi_scratch_bytes bytes, or NULL for the walk's
+ * per-device library scratch (zscrc_device_walk_multi).  ZSCRC_EINVAL before
+ * any device call: d_arena, images, d_rows or d_tot NULL; k == 0 or above
+ * ZSCRC_WALK_MULTI_MAX; an image with off > arena_size or size > arena_size -
+ * off; cap > 0 with d_recs NULL; flags != 0; misaligned scratch; bad options;
+ * more than 2^24 - 1 blocks over all images. */
+int zscrc_device_records_multi(const void *d_arena, uint64_t arena_size,
+                               const zscrc_walk_image *images, size_t k,
+                               struct zscrc_zs_record *d_recs, size_t cap,
+                               uint64_t *d_rows, uint64_t *d_tot, void *scratch,
+                               const zscrc_walk_opts *opts, unsigned flags, void *stream);
+
 /* The packed-file writer on the device: zscrc_pack_open / _add / _close
  * (further down) for a record list and its bytes that live in device memory --
  * d_out[0 .. file_bytes) receives exactly the bytes the host writer puts into

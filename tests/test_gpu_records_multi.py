@@ -1,0 +1,439 @@
+"""zscrc_device_records_multi (zeroskip_amd/csrc/zscrc_walk.hip)
+against the host lister (zscrc_zs_records, tests/records_images.host_records)
+of each image's own bytes: the records of k images of one device buffer listed
+in one call, offsets into the buffer, a row per image and the totals, equal
+word for word.  The rows and the totals are folded from the host lists in
+numpy; row words [2] and [8] come from following the host's records through
+the image (the only thing restated here is the length of a commit record).
+Images lie at offsets that are no multiples of 8 with canary bytes around
+them; output arrays are longer than `cap` and checked to be untouched past
+what a call may write."""
+import random
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import zs_format as zf
+from tests import fuzzlib
+from tests import records_images as ri
+from tests import walk_images as wi
+from tests.test_format_oracle import UUID, build_active
+from tests.test_gpu_merge import UUIDSTR
+from tests.test_gpu_records import _folds, unaligned_records_image
+from tests.test_gpu_walk_multi import CANARY, CANARY_WORD, PAD, _arena, _canary, _finalised, _key70k, _stopped
+from zeroskip_amd import repack, zsfile
+
+pytestmark = pytest.mark.gpu
+
+A = zsfile.ACTIVE
+ROW, TOT = zsfile.RECORDS_ROW_WORDS, zsfile.RECORDS_TOT_WORDS
+U64_MAX = (1 << 64) - 1
+EINVAL_WORD = U64_MAX                # (uint64_t)(int64_t)ZSCRC_EINVAL
+GEOMETRIES = [(64, 64), (512, 64), (4096, 512), (0, 0)]
+GEOMETRY_IDS = ["b64_t64", "b512_t64", "b4096_t512", "default"]
+
+
+# ------------------------------------------------------------------ helpers
+def _odd_gaps(images):
+    """Canary bytes before each image so that image i starts at an offset ==
+    1 + i % 7 (mod 8): never a multiple of 8, every other residue in turn."""
+    gaps, pos = [], 0
+    for i, img in enumerate(images):
+        gap = 8 + (1 + i % 7 - pos - 8) % 8
+        gaps.append(gap)
+        pos += gap + len(img)
+    return gaps
+
+
+def _trajectory(img: bytes, h: np.ndarray, rc: int):
+    """(row word [2], row word [8]) of an image of 40 bytes and more from its
+    host list: the lister's offsets from 40 -- a listed record leads to the
+    end of its value (or of its key, a delete), a commit record is 8 or 24
+    bytes, anything else is where the lister ended -- and the first of them
+    that is no multiple of 8."""
+    size, off, i, take = len(img), 40, 0, U64_MAX
+    while off < size:
+        if off % 8 and take == U64_MAX:
+            take = off
+        if i < len(h) and int(h[i][0]) == off + 24:
+            _, klen, voff, vlen = (int(v) for v in h[i])
+            off = off + 24 + zf.rup8(klen) if voff == U64_MAX else voff + zf.rup8(vlen)
+            i += 1
+            continue
+        rl = {zf.REC_COMMIT: 8, zf.REC_LONG_COMMIT: 24}.get(img[off]) if size - off >= 8 else None
+        if rl is None or size - off < rl:
+            break
+        off += rl
+    assert i == len(h) and (off == size) == (rc == zsfile.END), (i, len(h), off, size, rc)
+    if rc != zsfile.END:
+        # the image cut where the lister ended lists the same records and ends there
+        ch, crc = ri.host_records(img[:off], A)
+        assert crc == zsfile.END and np.array_equal(ch, h), off
+    return off, take
+
+
+def _host_image(img: bytes):
+    """(records uint64 [n, 4], row words [0..8]) of one image from the host lister."""
+    if len(img) < 40:
+        return np.zeros((0, 4), np.uint64), [EINVAL_WORD, 0, 0, 0, 0, 0, 0, 0, U64_MAX]
+    h, rc = ri.host_records(bytes(img), A)
+    assert rc in (zsfile.END, zsfile.STOPPED, zsfile.TRUNCATED)
+    end, take = _trajectory(bytes(img), h, rc)
+    return h, [rc, len(h), end] + _folds(h) + [take]
+
+
+def _expect(images, descs, took_over=None):
+    """What the one call must give for these images at these places:
+    (recs [n, 4], rows [k, 12], tot[1..7])."""
+    recs, rows, first, bad = [], [], 0, 0
+    for j, (img, (at, size)) in enumerate(zip(images, descs)):
+        assert size == len(img)
+        h, row = _host_image(img)
+        if took_over is not None:        # the builder's own word on where the lister leaves the slots
+            assert row[8] == took_over.get(j, U64_MAX), (j, row[8])
+        r = h.copy()
+        r[:, 0] += np.uint64(at)
+        r[r[:, 2] != U64_MAX, 2] += np.uint64(at)
+        recs.append(r)
+        rows.append(row + [first, 0, 0])
+        first += len(h)
+        bad += row[0] != zsfile.END
+    recs = np.concatenate(recs)
+    return recs, np.array(rows, np.uint64), [first] + _folds(recs) + [bad]
+
+
+def _run(d_arena, descs, cap=None, block=0, tile=0, scratch=None, null_recs=False):
+    """device_records_multi into canary-filled arrays PAD entries longer than
+    needed; the whole arrays come back as numpy uint64."""
+    dev, k = d_arena.device, len(descs)
+    if cap is None:
+        cap = sum(size // 24 + 1 for _, size in descs)
+    room = 0 if null_recs else cap + PAD
+    out = (_canary(32 * room, dev).view(torch.int64).view(room, 4), _canary(8 * (ROW * k + PAD), dev).view(torch.int64),
+           _canary(8 * (TOT + PAD), dev).view(torch.int64))
+    zsfile.device_records_multi(d_arena, descs, cap=cap, block_bytes=block, tile_bytes=tile, out=out, scratch=scratch)
+    recs, rows, tot = (t.cpu().numpy().view(np.uint64) for t in out)
+    return recs.reshape(room, 4), rows, tot, cap
+
+
+def _check(got, exp, what=""):
+    recs, rows, tot, cap = got
+    erecs, erows, etot = exp
+    k, total = len(erows), etot[0]
+    assert np.array_equal(rows[:ROW * k].reshape(k, ROW), erows), (what, rows[:ROW * k].reshape(k, ROW), erows)
+    assert [int(v) for v in tot[:TOT]] == [zsfile.OVERFLOW if total > cap else 0] + etot, (what, tot[:TOT], etot)
+    m = min(total, cap)
+    assert np.array_equal(recs[:m], erecs[:m]), what
+    # nothing at index >= min(total, cap) was written, nor past the rows and the totals
+    assert (recs[m:] == CANARY_WORD).all(), what
+    assert (rows[ROW * k:] == CANARY_WORD).all() and (tot[TOT:] == CANARY_WORD).all(), what
+
+
+def _both(images, gaps=None, took_over=None, dev=None):
+    buf, descs = _arena(images, _odd_gaps(images) if gaps is None else gaps)
+    return torch.from_numpy(buf).to(dev), descs, _expect(images, descs, took_over)
+
+
+def _one_record() -> bytes:
+    im = wi.Img()
+    im.add(zf.key_record(b"only") + zf.value_record(b"one record"))
+    return im.image()
+
+
+def _mixed(default: bool):
+    """The arena of test_mixed_arena: (images, names)."""
+    good = build_active(50, seed=21)
+    several = wi.big_image() if default else build_active(200, seed=11)     # several blocks at every geometry
+    named = [("empty", b""), ("39_bytes", zf.header_bytes(UUID, 1, 1)[:39]), ("40_bytes", zf.header_bytes(UUID, 1, 1)),
+             ("one_record", _one_record()), ("finalised_300", ri.finalised_300()), ("deletes", ri.wellformed()),
+             ("key_70k", _key70k()), ("several_blocks", several), ("stopped", _stopped()),
+             ("truncated", good[:len(good) * 2 // 3 + 3])]
+    named += [(name, img) for name, img, _, _ in ri.disagreement_images()]
+    return [img for _, img in named], [name for name, _ in named]
+
+
+@pytest.fixture(scope="module")
+def mixed_small():
+    images, names = _mixed(False)
+    return images, names, _arena(images, _odd_gaps(images))
+
+
+@pytest.fixture(scope="module")
+def tails():
+    """Ordinary images before, between and after two images whose lister goes
+    one-lane in the middle: (images, {index: the first unaligned offset})."""
+    t1, first1, n1 = unaligned_records_image(build_active(30, seed=2))
+    t2, first2, n2 = unaligned_records_image(ri.wellformed())
+    images = [build_active(6, seed=31), t1, build_active(3, seed=32), b"", t2, build_active(1, seed=35)]
+    return images, {1: first1, 4: first2}, (n1, n2)
+
+
+# -------------------------------------------------------------------- tests
+@pytest.mark.parametrize("block,tile", GEOMETRIES, ids=GEOMETRY_IDS)
+def test_mixed_arena(gpu, mixed_small, block, tile):
+    if block:
+        images, names, (buf, descs) = mixed_small
+    else:
+        images, names = _mixed(True)
+        buf, descs = _arena(images, _odd_gaps(images))
+    assert all(off % 8 for off, _ in descs) and len({off % 8 for off, _ in descs}) == 7
+    exp = _expect(images, descs)
+    rows = {name: [int(v) for v in row] for name, row in zip(names, exp[1])}
+    assert rows["empty"][0] == rows["39_bytes"][0] == EINVAL_WORD and rows["40_bytes"][:3] == [zsfile.END, 0, 40]
+    assert rows["one_record"][1] == 1 and rows["deletes"][3] > 0 and rows["key_70k"][6] >= 70000
+    assert len(images[names.index("several_blocks")]) > 2 * (block or wi.DEF_BLOCK)
+    assert rows["stopped"][0] == zsfile.STOPPED and rows["truncated"][0] == zsfile.TRUNCATED
+    assert rows["commit_span_exceeds_offset"][0] == zsfile.END and rows["value_offset_inside_key"][0] == zsfile.TRUNCATED
+    assert exp[2][6] == 6                 # two too short, stopped, truncated, two of the disagreement images
+    _check(_run(torch.from_numpy(buf).to(gpu), descs, block=block, tile=tile), exp, (block, tile))
+
+
+def test_image_ends_on_record_then_next_image(gpu):
+    im = wi.Img()
+    im.add(zf.key_record(b"k" * 20) + zf.value_record(b"v" * 333))
+    im.add(wi.short_commit(len(im) - 40))
+    im.add(zf.key_record(b"last-key") + zf.value_record(b"w" * 64))
+    first = im.image()
+    h, rc = ri.host_records(first, A)
+    assert rc == zsfile.END and int(h[-1][2] + h[-1][3]) == len(first)     # its last record ends at its last byte
+    second = build_active(7, seed=4)
+    for lead in (8, 11):                                    # an aligned and an unaligned place
+        buf, descs = _arena([first, second], gaps=[lead, 0])
+        assert descs[1][0] == descs[0][0] + len(first)      # no byte between the two
+        d = torch.from_numpy(buf).to(gpu)
+        exp = _expect([first, second], descs)
+        _check(_run(d, descs), exp, "whole")
+        _check(_run(d, descs, block=64, tile=64), exp, "whole b64")
+        for cut in (8, 4):
+            # the same bytes, the first image declared `cut` bytes shorter: its last record no longer
+            # fits, and the second image's bytes that follow its end belong to no record of it
+            short = first[:-cut]
+            cd = [(descs[0][0], len(short)), descs[1]]
+            exp = _expect([short, second], cd)
+            assert [int(v) for v in exp[1][0][:2]] == [zsfile.TRUNCATED, len(h) - 1]
+            _check(_run(d, cd), exp, ("cut", cut))
+            _check(_run(d, cd, block=64, tile=64), exp, ("cut b64", cut))
+
+
+def test_caps(gpu, tails):
+    images, took, _ = tails
+    d, descs, exp = _both(images, took_over=took, dev=gpu)
+    total, at2, at4 = exp[2][0], int(exp[1][2][9]), int(exp[1][4][9])
+    assert 2 < at2 < at4 < total - 2
+    for block, tile in ((0, 0), (64, 64)):
+        # no array at all; an image boundary; the middle of an image; around the total
+        _check(_run(d, descs, cap=0, null_recs=True, block=block, tile=tile), exp, ("cap 0, no array", block))
+        for cap in (0, 1, at2 - 1, at2, at2 + 1, at4, at4 + 2, total - 1, total, total + 1):
+            got = _run(d, descs, cap=cap, block=block, tile=tile)
+            assert int(got[2][0]) == (zsfile.OVERFLOW if cap < total else 0) and int(got[2][1]) == total
+            _check(got, exp, (cap, block))
+
+
+@pytest.mark.parametrize("block,tile", GEOMETRIES, ids=GEOMETRY_IDS)
+def test_counted_tails(gpu, tails, block, tile):
+    """Two counted tails of two records each (a delete and a key / value
+    record at offsets = 4 mod 8, behind a crafted record whose value ends at
+    such an offset): row [8] names where the
+    one-lane loop took over, the images behind a tail take their row [9] from
+    its count, and the tail's records are in the sums and maxima once."""
+    images, took, (n1, n2) = tails
+    d, descs, exp = _both(images, took_over=took, dev=gpu)
+    recs, rows, tot = exp
+    assert [int(rows[j][8]) for j in (1, 4)] == [took[1], took[4]] and all(v % 8 == 4 for v in took.values())
+    assert (int(rows[1][1]), int(rows[4][1])) == (n1 + 3, n2 + 3)
+    assert int(rows[2][9]) == int(rows[1][9]) + n1 + 3 and int(rows[5][9]) == int(rows[4][9]) + n2 + 3
+    for j, n0 in ((1, n1), (4, n2)):
+        base, at = int(rows[j][9]), descs[j][0]
+        crafted, tail = recs[base + n0], recs[base + n0 + 1:base + n0 + 3]
+        assert int(crafted[0]) == at + took[j] - 52 + 24
+        assert [int(v) for v in tail[:, 0]] == [at + took[j] + 24, at + took[j] + 32 + 24]
+        assert int(tail[0][2]) == U64_MAX and [int(v) for v in tail[:, 1]] == [8, 8]
+        # the row's folds are those of the records before the tail and of the tail together
+        head = ri.host_records(images[j][:took[j] - 52], A)[0]
+        own = recs[base:base + n0 + 3]
+        assert len(head) == n0 and int(rows[j][4]) == _folds(head)[1] + 4 + 16 == _folds(own)[1]
+        assert int(rows[j][3]) == _folds(head)[0] + 1
+    got = _run(d, descs, block=block, tile=tile)
+    _check(got, exp, (block, tile))
+    first_tail = int(rows[1][9]) + n1 + 1
+    for cap in (first_tail - 1, first_tail, first_tail + 1, first_tail + 2, int(rows[4][9]) + n2 + 2):
+        _check(_run(d, descs, cap=cap, block=block, tile=tile), exp, (cap, block))
+
+
+def test_order_repeat_overlap(gpu):
+    images = [build_active(12, seed=41), build_active(5, seed=42), ri.finalised_300(), build_active(1, seed=43)]
+    buf, descs = _arena(images, _odd_gaps(images))
+    d = torch.from_numpy(buf).to(gpu)
+    rev = list(reversed(range(len(images))))
+    assert [descs[i][0] for i in rev] == sorted((o for o, _ in descs), reverse=True)
+    _check(_run(d, [descs[i] for i in rev]), _expect([images[i] for i in rev], [descs[i] for i in rev]), "descending")
+    order = [2, 0, 2, 1]
+    _check(_run(d, [descs[i] for i in order], block=512, tile=64),
+           _expect([images[i] for i in order], [descs[i] for i in order]), "repeated")
+    # a descriptor over the last bytes of an image: the host list of those bytes (whatever they hold
+    # from their 40th byte on), and one over its first half
+    big = images[2]
+    for cut in (len(big) // 2, len(big) // 2 + 3, len(big) - 41):
+        suffix, half = big[cut:], big[:cut + 4]
+        dd = [descs[2], (descs[2][0] + cut, len(suffix)), (descs[2][0], len(half)), descs[0]]
+        exp = _expect([big, suffix, half, images[0]], dd)
+        _check(_run(d, dd), exp, ("overlap", cut))
+        _check(_run(d, dd, block=64, tile=64), exp, ("overlap b64", cut))
+
+
+def test_many_images(gpu):
+    # more images than one workgroup of the chain launch (256) and than one chunk of the scan (1024)
+    images = [build_active(i % 4, seed=i) for i in range(2000)]
+    assert all(40 <= len(m) < 8192 for m in images)      # from a bare header to a few KB
+    d, descs, exp = _both(images, dev=gpu)
+    assert exp[2][0] > 2000 and exp[2][6] == 0
+    for block, tile in ((0, 0), (64, 64)):
+        _check(_run(d, descs, block=block, tile=tile), exp, (block, tile))
+
+
+def test_caller_scratch_fenced(gpu, tails):
+    images, took, _ = tails
+    for block, tile in ((0, 0), (512, 64)):
+        d, descs, exp = _both(images, took_over=took, dev=gpu)
+        need = zsfile.records_multi_scratch_bytes(descs, block, tile)
+        assert need > 0
+        whole = _canary(need + 2 * 4096, gpu)
+        scratch = whole[4096:4096 + need]
+        assert scratch.data_ptr() % 16 == 0
+        mine = _run(d, descs, block=block, tile=tile, scratch=scratch)
+        _check(mine, exp, ("caller scratch", block))
+        h = whole.cpu().numpy()
+        assert (h[:4096] == CANARY).all() and (h[4096 + need:] == CANARY).all()
+        lib = _run(d, descs, block=block, tile=tile)
+        assert all(np.array_equal(a, b) for a, b in zip(mine[:3], lib[:3]))
+
+
+def test_library_scratch_across_streams(gpu, tails):
+    """The library's scratch from two streams: a walk on the default stream,
+    the record lists on a side stream right behind it, and the reverse."""
+    images, took, _ = tails
+    d, descs, exp = _both(images, took_over=took, dev=gpu)
+    one = build_active(200, seed=11)
+    d_one = torch.from_numpy(np.frombuffer(one, dtype=np.uint8).copy()).to(gpu)
+    hoff, hlen, hrc, hend = wi.host_walk(one)
+    side = torch.cuda.Stream(device=gpu)
+    torch.cuda.synchronize(gpu)
+
+    def walk_ok(res):
+        off, ln, r = res
+        r = r.cpu().numpy().view(np.uint64)
+        assert (int(r[0]), int(r[1]), int(r[2])) == (hrc, len(hoff), hend)
+        assert np.array_equal(off[:len(hoff)].cpu().numpy().view(np.uint64), hoff)
+        assert np.array_equal(ln[:len(hoff)].cpu().numpy().view(np.uint64), hlen)
+
+    single = zsfile.device_walk(d_one, block_bytes=512, tile_bytes=64)
+    with torch.cuda.stream(side):
+        multi = _run(d, descs)
+    torch.cuda.synchronize(gpu)
+    walk_ok(single)
+    _check(multi, exp, "lists behind a walk")
+    recs, rows, tot = zsfile.device_records_multi(d, descs, block_bytes=512, tile_bytes=64)
+    with torch.cuda.stream(side):
+        single = zsfile.device_walk(d_one)
+    torch.cuda.synchronize(gpu)
+    walk_ok(single)
+    assert np.array_equal(recs[:exp[2][0]].cpu().numpy().view(np.uint64), exp[0])
+    assert np.array_equal(rows.cpu().numpy().view(np.uint64), exp[1])
+
+
+def test_two_runs_bit_for_bit(gpu, mixed_small):
+    images, _, (buf, descs) = mixed_small
+    d = torch.from_numpy(buf).to(gpu)
+    for block, tile in ((0, 0), (4096, 512)):
+        a, b = _run(d, descs, block=block, tile=tile), _run(d, descs, block=block, tile=tile)
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(a[:3], b[:3]))
+
+
+def test_fuzz(gpu):
+    """120 fuzzlib mutants of four well-formed images, 40 an arena, against the
+    host lister.  (Every device step is bounded by construction: a mutant can
+    only list differently, never run longer.)"""
+    w = zf.FileWriter(UUID, idx=2)
+    for t in range(6):
+        for i in range(40):
+            w.add(b"%08d" % (t * 100 + i), bytes([i]) * (i * 7 % 200))
+        w.commit()
+    bases = [build_active(30, seed=2), w.image(), _key70k(), _finalised()]
+    rng = random.Random(19)
+    imgs = [fuzzlib.mutate(rng, rng.choice(bases)) for _ in range(120)]
+    seen = set()
+    for a in range(0, len(imgs), 40):
+        group = imgs[a:a + 40]
+        buf, descs = _arena(group, _odd_gaps(group))
+        d = torch.from_numpy(buf).to(gpu)
+        exp = _expect(group, descs)
+        seen |= {int(row[0]) for row in exp[1]}
+        for block, tile in ((512, 64), (0, 0)):
+            _check(_run(d, descs, block=block, tile=tile), exp, (a, block, tile))
+    print("host lister results among the mutants:", sorted(seen))
+    assert {zsfile.END, zsfile.STOPPED, zsfile.TRUNCATED} <= seen  # a condition on the inputs
+
+
+# ------------------------------------------------------------- feed-through
+def _finalised_files(k: int):
+    rng = np.random.default_rng(12)
+    images = []
+    for idx in range(3, 3 + k):
+        w = zf.FileWriter(UUID, idx=idx)
+        for t in range(40):
+            key = b"%016d" % int(rng.integers(0, 150))
+            if t % 7 == 3:
+                w.remove(key)
+            else:
+                w.add(key, rng.integers(0, 256, int(rng.integers(0, 90)), dtype=np.uint8).tobytes())
+            w.commit()
+        images.append(w.image())
+    return images
+
+
+def test_one_list_merges_as_the_k_lists(gpu):
+    images = _finalised_files(5)
+    buf, descs = _arena(images, _odd_gaps(images))
+    d = torch.from_numpy(buf).to(gpu)
+    recs, rows, tot = zsfile.device_records_multi(d, descs)
+    t = [int(v) for v in tot.cpu()]
+    assert t[0] == 0 and t[7] == 0 and t[1] == 5 * 40
+    per = []
+    for off, size in descs:
+        r, res = zsfile.device_records(d[off:off + size], zsfile.FINALISED)
+        per.append((r[:int(res[1])], off))
+    for drop in (False, True):
+        one, ores = repack.device_merge(d, [(recs[:t[1]], 0)], drop_deletes=drop)
+        many, mres = repack.device_merge(d, per, drop_deletes=drop)
+        assert ores.cpu().tolist() == mres.cpu().tolist() and int(ores[0]) == 0 and 0 < int(ores[1]) < 200
+        assert one.cpu().numpy().tobytes() == many.cpu().numpy().tobytes()
+
+
+def test_device_repack_twelve_finalised_files(gpu, tmp_path):
+    images = _finalised_files(12)
+    merged = zf.repack_finalised(images)
+    assert any(v is None for _, v in merged) and len(merged) < 12 * 40      # deletes kept, keys overlap
+    want = zf.packed_file(merged, UUID, 3, 14)
+    buf, at = _arena(images, [64 - len(m) % 64 for m in [b""] + images[:-1]])
+    arena = torch.from_numpy(buf).to(gpu)
+    img, rep = repack.device_repack(arena, at, [zsfile.FINALISED] * 12, UUID, 3, 14, drop_deletes=False)
+    assert img.cpu().numpy().tobytes() == want
+    assert rep["records_in"] == 12 * 40 and rep["records_out"] == len(merged) and rep["deletes_dropped"] == 0
+    assert rep["records_out"] + rep["superseded"] == 12 * 40 and rep["file_bytes"] == len(want)
+    # the same DB on disk through the host repack
+    for idx, image in zip(range(3, 15), images):
+        (tmp_path / f"zeroskip-{UUIDSTR}-{idx}-{idx}").write_bytes(image)
+    (tmp_path / ".zsdb").write_bytes(zf.dotzsdb_bytes(4096, UUIDSTR.encode() + b"\0", 15))
+    host = repack.repack_dir(str(tmp_path))
+    assert host["branch"] == 1 and (host["startidx"], host["endidx"]) == (3, 14)
+    assert open(host["path"], "rb").read() == img.cpu().numpy().tobytes()
+    assert host["records_in"] == rep["records_in"] and host["records_out"] == rep["records_out"]
+
+
+def test_device_repack_names_the_first_image_that_does_not_list(gpu):
+    images = _finalised_files(4)
+    images[2] = images[2][:len(images[2]) // 2 + 3]
+    buf, at = _arena(images, _odd_gaps(images))
+    with pytest.raises(ValueError, match="image at %d does not list: code %d" % (at[2][0], zsfile.TRUNCATED)):
+        repack.device_repack(torch.from_numpy(buf).to(gpu), at, [zsfile.FINALISED] * 4, UUID, 3, 6, drop_deletes=False)

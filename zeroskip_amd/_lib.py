@@ -106,7 +106,9 @@ SIGNATURES = {
     "zscrc_device_verify_images": (_int, [_vp, _u64, _vp, _sz, _vp, _vp]),
     "zscrc_device_records_scratch_bytes": (_sz, [_u64, _int, _vp]),
     "zscrc_device_records": (_int, [_vp, _u64, _int, _vp, _sz, _vp, _vp, _vp, ctypes.c_uint, _vp]),
-    "zscrc_device_pack_bound": (_u64, [_u64, _u64, _u64]),
+    "zscrc_device_records_multi_scratch_bytes": (_sz, [_vp, _sz, _vp]),
+    "zscrc_device_records_multi": (_int, [_vp, _u64, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, ctypes.c_uint, _vp]),
+    "zscrc_device_pack_bound":(_u64, [_u64, _u64, _u64]),
     "zscrc_device_pack_scratch_bytes": (_sz, [_sz, _vp]),
     "zscrc_device_pack": (_int, [_vp, _u64, _vp, _sz, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, ctypes.c_uint,
                                  _vp]),

@@ -47,6 +47,8 @@
  * images (the lister never looks at a commit's span length, the walk never at
  * a key length), so neither can use the other's tables.  Packed images have no
  * chain: records_packed_*_kernel parse the pointer section one pointer a thread.
+ * zscrc_device_records_multi is RecordList over many images, the fourth
+ * combination: the many-image walk's four launches with this policy.
  *
  * Shared with the other device stages: the record words and types
  * (zscrc_records.h), the many-image walk's scan of the counts (scan_counts,
@@ -301,6 +303,9 @@ struct CommitWalk {
         uint64_t mx = 0, mn = U64_MAX;
     };
     static constexpr int FOLD = 2;
+    /* the many-image rows: words a row, the take-over word, the first-index word */
+    static constexpr int ROW = ZSCRC_WALK_ROW_WORDS, TAKE = 5, FIRST = 6;
+    static constexpr bool TOT_NOT_END = false;
     static __device__ __forceinline__ S step_w(const uint8_t *img, uint64_t size, uint64_t off, uint64_t w)
     {
         return ::step_w(img, size, off, w);
@@ -322,12 +327,23 @@ struct CommitWalk {
             fold_lengths(w, acc.mx, acc.mn);
     }
     static __device__ __forceinline__ bool folded(const uint64_t (&w)[FOLD]) { return w[1] != U64_MAX; }
+    static __device__ __forceinline__ void acc_words(const Acc &acc, uint64_t (&w)[FOLD])
+    {
+        w[0] = acc.mx;
+        w[1] = acc.mn;
+    }
     template <bool MULTI>
     static __device__ __forceinline__ void fold_out(const Walk &a, const Multi &m, uint64_t *w)
     {
         fold_lengths(a.res + 3, w[0], w[1]);
         if constexpr (MULTI)
             fold_lengths(m.tot + 2, w[0], w[1]);
+    }
+    /* the totals' fold words [2] and [3] for n commits; `bad` is not kept */
+    static __device__ __forceinline__ void tot_init(uint64_t *tot, uint64_t n, uint64_t)
+    {
+        tot[2] = 0;
+        tot[3] = n ? U64_MAX : 0;
     }
     /* the emit launch folds the blocks' lengths into [3] and [4] */
     static __device__ __forceinline__ void finish(const Walk &a, int rc, uint64_t n, uint64_t end, const Acc &acc,
@@ -356,6 +372,9 @@ struct RecordList {
         uint64_t del = 0, klen = 0, vlen = 0, kmax = 0, vmax = 0;
     };
     static constexpr int FOLD = 5;
+    static constexpr int ROW = ZSCRC_RECORDS_ROW_WORDS, TAKE = 8, FIRST = 9;
+    static constexpr bool TOT_NOT_END = true;
+    static_assert(ROW == ZSCRC_RECORDS_RES_WORDS, "finish writes a row");
     /* zsrec::L_SKIP / L_RECORD / L_TRUNC / L_STOP are S_ADV / S_OUT / S_TRUNC / S_STOP */
     static __device__ __forceinline__ S step_w(const uint8_t *img, uint64_t size, uint64_t off, uint64_t w)
     {
@@ -384,11 +403,20 @@ struct RecordList {
         o[3] = r.val_len;
     }
     template <bool MULTI>
-    static __device__ __forceinline__ void put(const Walk &a, const Multi &, uint64_t rank, uint64_t, const S &s,
+    static __device__ __forceinline__ void put(const Walk &a, const Multi &m, uint64_t rank, uint64_t, const S &s,
                                                Acc &acc)
     {
-        if (rank < a.cap)
-            store_rec(a.off, rank, s.rec);
+        if (rank < a.cap) {
+            if constexpr (MULTI) { /* offsets into the arena; an image lies inside it: no wrap */
+                zscrc_zs_record r = s.rec;
+                r.key_off += m.add;
+                if (r.val_off != ZSCRC_ZS_DELETED)
+                    r.val_off += m.add;
+                store_rec(a.off, rank, r);
+            } else {
+                store_rec(a.off, rank, s.rec);
+            }
+        }
         fold_rec(s.rec, acc);
     }
     static __device__ __forceinline__ void fold_init(uint64_t *w)
@@ -417,10 +445,27 @@ struct RecordList {
         fold_words(w, acc.del, acc.klen, acc.vlen, acc.kmax, acc.vmax);
     }
     static __device__ __forceinline__ bool folded(const uint64_t (&w)[FOLD]) { return (w[0] | w[1] | w[2]) != 0; }
+    static __device__ __forceinline__ void acc_words(const Acc &acc, uint64_t (&w)[FOLD])
+    {
+        w[0] = acc.del;
+        w[1] = acc.klen;
+        w[2] = acc.vlen;
+        w[3] = acc.kmax;
+        w[4] = acc.vmax;
+    }
     template <bool MULTI>
-    static __device__ __forceinline__ void fold_out(const Walk &a, const Multi &, uint64_t *w)
+    static __device__ __forceinline__ void fold_out(const Walk &a, const Multi &m, uint64_t *w)
     {
         fold_words(a.res + 3, w[0], w[1], w[2], w[3], w[4]);
+        if constexpr (MULTI)
+            fold_words(m.tot + 2, w[0], w[1], w[2], w[3], w[4]);
+    }
+    /* the totals' fold words [2] .. [6], and [7]: the images that do not list to their end */
+    static __device__ __forceinline__ void tot_init(uint64_t *tot, uint64_t, uint64_t bad)
+    {
+        for (int i = 0; i < FOLD; ++i)
+            tot[2 + i] = 0;
+        tot[7] = bad;
     }
     /* the emit launch folds the blocks' records into [3] .. [7] */
     static __device__ __forceinline__ void finish(const Walk &a, int rc, uint64_t n, uint64_t end, const Acc &acc,
@@ -902,6 +947,13 @@ __global__ __launch_bounds__(WG) void records_packed_emit_kernel(Packed a)
  *   walk_multi_emit_kernel   one workgroup per (image, block): emit_sweep from
  *                            row[6]; and one lane per image that walks a
  *                            counted tail again, storing its spans
+ *
+ * zscrc_device_records_multi is the same four launches with the RecordList
+ * policy (records_multi_*_kernel): each family is multi_table / multi_chain /
+ * multi_scan / multi_emit below with its policy, which also names the row's
+ * layout (P::ROW words; P::TAKE the take-over word, [5] above; P::FIRST the
+ * first-index word, [6] above).  The records family sweeps tables of its own.
+ * A counted tail is folded in the emit launch only, where it is stored.
  */
 struct ImgD {
     uint64_t off, size;   /* the image: bytes [off, off + size) of the arena */
@@ -913,15 +965,15 @@ struct ImgD {
 struct MWalk {
     const uint8_t *arena;
     const ImgD *im;       /* scratch: k + 1, the last one holds the totals */
-    uint64_t *tail_n;     /* scratch: k, the commits before a counted tail */
+    uint64_t *tail_n;     /* scratch: k, the commits (records) before a counted tail */
     Entry *entry;         /* scratch: every image's blocks */
     uint32_t *J, *C;      /* scratch: every image's slots */
     uint32_t k, nblocks;
     uint32_t bs, ts, rounds;
-    uint64_t *off, *len;
+    uint64_t *off, *len;  /* the spans (the record lister: off = the entries, four words each; len, img unused) */
     uint32_t *img;
     uint64_t cap;
-    uint64_t *rows, *tot;
+    uint64_t *rows, *tot; /* k rows of P::ROW words; the totals */
 };
 
 constexpr uint64_t MULTI_MAX = ZSCRC_WALK_MULTI_MAX;
@@ -943,7 +995,9 @@ __device__ __forceinline__ uint32_t image_of(const MWalk &a, uint32_t blk)
     return lo;
 }
 
-/* Image j as the single walk sees it; its spans go to the shared arrays. */
+/* Image j as the single walk of policy P sees it; its output goes to the
+ * shared arrays, its result words to its row. */
+template <class P>
 __device__ __forceinline__ Walk view_of(const MWalk &a, uint32_t j)
 {
     const ImgD d = a.im[j];
@@ -961,87 +1015,111 @@ __device__ __forceinline__ Walk view_of(const MWalk &a, uint32_t j)
     w.off = a.off;
     w.len = a.len;
     w.cap = a.cap;
-    w.res = a.rows + (uint64_t)j * ROW;
+    w.res = a.rows + (uint64_t)j * P::ROW;
     return w;
 }
 
-__global__ __launch_bounds__(WG) void walk_multi_table_kernel(MWalk a)
+template <class P>
+__device__ __forceinline__ void multi_table(const MWalk &a)
 {
     const uint32_t j = image_of(a, blockIdx.x);
-    const Walk w = view_of(a, j);
+    const Walk w = view_of<P>(a, j);
     const uint32_t blk = blockIdx.x - a.im[j].blk0;
     if (threadIdx.x == 0)
         w.entry[blk].slot = NONE;
-    table_sweep<CommitWalk>(w, blk);
+    table_sweep<P>(w, blk);
 }
 
-__global__ __launch_bounds__(WG) void walk_multi_chain_kernel(MWalk a)
+/* One lane per image: the row as P::finish writes the result words of that
+ * image alone with unlimited room (so [0] is never OVERFLOW), the fold words
+ * at their initial values; the words after P::FIRST 0. */
+template <class P>
+__device__ __forceinline__ void multi_chain(const MWalk &a)
 {
     const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
     if (j >= a.k)
         return;
-    const Walk w = view_of(a, (uint32_t)j);
-    uint64_t *row = w.res;
-    row[3] = 0;
-    row[7] = 0;
-    if (w.size < HDR) { /* no walk: zscrc_zs_walk's ZSCRC_EINVAL */
-        row[0] = (uint64_t)(int64_t)ZSCRC_EINVAL;
-        row[1] = row[2] = row[4] = 0;
-        row[5] = U64_MAX;
+    Walk w = view_of<P>(a, (uint32_t)j);
+    w.cap = U64_MAX;
+    for (int i = P::FIRST + 1; i < P::ROW; ++i)
+        w.res[i] = 0;
+    if (w.size < HDR) { /* nothing to walk: the host loop's ZSCRC_EINVAL */
+        P::finish(w, ZSCRC_EINVAL, 0, 0, typename P::Acc{}, U64_MAX);
         return;
     }
     uint64_t n, end, unaligned;
-    int rc = chain_hops<CommitWalk>(w, n, end, unaligned);
+    int rc = chain_hops<P>(w, n, end, unaligned);
     a.tail_n[j] = n;
-    if (unaligned != U64_MAX) { /* the spans' positions are not known yet: count */
+    if (unaligned != U64_MAX) { /* the output positions are not known yet: count */
         end = unaligned;
-        rc = serial_loop<CommitWalk>(w, end, [&n](uint64_t, const Step &) { ++n; });
+        rc = serial_loop<P>(w, end, [&n](uint64_t, const typename P::S &) { ++n; });
     }
-    row[0] = (uint64_t)rc;
-    row[1] = n;
-    row[2] = end;
-    row[4] = n ? U64_MAX : 0;
-    row[5] = unaligned;
+    P::finish(w, rc, n, end, typename P::Acc{}, unaligned);
 }
 
-__global__ __launch_bounds__(WG) void walk_multi_scan_kernel(MWalk a)
+/* One workgroup: row[P::FIRST] = exclusive prefix sum of the counts
+ * (scan_counts, zscrc_wg.h); the totals, their fold words at the initial
+ * values the emit launch folds into. */
+template <class P>
+__device__ __forceinline__ void multi_scan(const MWalk &a)
 {
     __shared__ uint64_t s_scan[WG / 64];
     const uint64_t carry = scan_counts(
-        s_scan, a.k, [&a](uint64_t i) { return a.rows[i * ROW + 1]; },
-        [&a](uint64_t i, uint64_t at) { a.rows[i * ROW + 6] = at; });
+        s_scan, a.k, [&a](uint64_t i) { return a.rows[i * P::ROW + 1]; },
+        [&a](uint64_t i, uint64_t at) { a.rows[i * P::ROW + P::FIRST] = at; });
+    uint64_t bad = 0; /* images whose row [0] is not END, where the totals have a word for them */
+    if constexpr (P::TOT_NOT_END) {
+        for (uint64_t i = threadIdx.x; i < a.k; i += WG)
+            bad += a.rows[i * P::ROW] != (uint64_t)ZSCRC_ZS_END;
+        bad = wg_sum(s_scan, bad);
+    }
     if (threadIdx.x == 0) {
         a.tot[0] = carry > a.cap ? (uint64_t)ZSCRC_ZS_OVERFLOW : 0;
         a.tot[1] = carry;
-        a.tot[2] = 0;
-        a.tot[3] = carry ? U64_MAX : 0; /* the emit launch folds the lengths into [2] and [3] */
+        P::tot_init(a.tot, carry, bad);
     }
 }
 
 /* Workgroup w: the emit sweep of block w (if there is one), then one lane per
  * image of [w * WG, w * WG + WG) for the counted tails (if there are such
- * images): a grid of max(blocks, ceil(k / WG)) workgroups. */
-__global__ __launch_bounds__(WG) void walk_multi_emit_kernel(MWalk a)
+ * images): a grid of max(blocks, ceil(k / WG)) workgroups.  A tail's records
+ * are stored from row[P::FIRST] + the records before the tail, and folded
+ * here and nowhere else. */
+template <class P>
+__device__ __forceinline__ void multi_emit(const MWalk &a)
 {
     if (blockIdx.x < a.nblocks) {
         const uint32_t j = image_of(a, blockIdx.x);
-        const Walk w = view_of(a, j);
-        emit_sweep<CommitWalk, true>(w, blockIdx.x - a.im[j].blk0, w.res[6], Multi{a.im[j].off, a.img, j, a.tot});
+        const Walk w = view_of<P>(a, j);
+        emit_sweep<P, true>(w, blockIdx.x - a.im[j].blk0, w.res[P::FIRST], Multi{a.im[j].off, a.img, j, a.tot});
     }
     const uint64_t j = (uint64_t)blockIdx.x * WG + threadIdx.x;
-    if (j >= a.k || a.rows[j * ROW + 5] == U64_MAX)
+    if (j >= a.k || a.rows[j * P::ROW + P::TAKE] == U64_MAX)
         return;
-    const Walk w = view_of(a, (uint32_t)j);
+    const Walk w = view_of<P>(a, (uint32_t)j);
     const Multi m{a.im[j].off, a.img, (uint32_t)j, a.tot};
-    uint64_t off = w.res[5], n = w.res[6] + a.tail_n[j], mx = 0, mn = U64_MAX;
-    (void)serial_loop<CommitWalk>(w, off, [&](uint64_t at, const Step &s) {
-        put_span<true>(w, m, n++, at - s.span, s.span, mx, mn);
+    uint64_t off = w.res[P::TAKE], n = w.res[P::FIRST] + a.tail_n[j];
+    typename P::Acc acc;
+    (void)serial_loop<P>(w, off, [&](uint64_t at, const typename P::S &s) {
+        P::template put<true>(w, m, n++, at, s, acc);
     });
-    if (mn != U64_MAX) {
-        fold_lengths(w.res + 3, mx, mn);
-        fold_lengths(a.tot + 2, mx, mn);
-    }
+    uint64_t f[P::FOLD];
+    P::acc_words(acc, f);
+    if (P::folded(f))
+        P::template fold_out<true>(w, m, f);
 }
+
+__global__ __launch_bounds__(WG) void walk_multi_table_kernel(MWalk a) { multi_table<CommitWalk>(a); }
+__global__ __launch_bounds__(WG) void walk_multi_chain_kernel(MWalk a) { multi_chain<CommitWalk>(a); }
+__global__ __launch_bounds__(WG) void walk_multi_scan_kernel(MWalk a) { multi_scan<CommitWalk>(a); }
+__global__ __launch_bounds__(WG) void walk_multi_emit_kernel(MWalk a) { multi_emit<CommitWalk>(a); }
+
+/* zscrc_device_records_multi: off = the record entries of all images (four
+ * words each), len and img unused, rows of ZSCRC_RECORDS_ROW_WORDS words. */
+__global__ __launch_bounds__(WG) void records_multi_table_kernel(MWalk a) { multi_table<RecordList>(a); }
+__global__ __launch_bounds__(WG) void records_multi_chain_kernel(MWalk a) { multi_chain<RecordList>(a); }
+__global__ __launch_bounds__(WG) void records_multi_scan_kernel(MWalk a) { multi_scan<RecordList>(a); }
+__global__ __launch_bounds__(WG) void records_multi_emit_kernel(MWalk a) { multi_emit<RecordList>(a); }
 
 /* The 40-byte headers of k images, one after another (zscrc_device_verify_images);
  * zeros for an image of fewer than 40 bytes. */
@@ -1187,15 +1265,41 @@ int stage_descriptors(Scratch &sc, const zscrc_walk_image *images, size_t k, con
     return zs::stage_copy(sc, d_desc, bytes, s);
 }
 
-int launch_multi(const MWalk &m, hipStream_t s)
+/* records: the record lister's instances instead of the commit walk's. */
+int launch_multi(const MWalk &m, hipStream_t s, bool records)
 {
     const unsigned lanes = (m.k + WG - 1) / WG;
     if (m.nblocks)
-        hipLaunchKernelGGL(walk_multi_table_kernel, dim3(m.nblocks), dim3(WG), 0, s, m);
-    hipLaunchKernelGGL(walk_multi_chain_kernel, dim3(lanes), dim3(WG), 0, s, m);
-    hipLaunchKernelGGL(walk_multi_scan_kernel, dim3(1), dim3(WG), 0, s, m);
-    hipLaunchKernelGGL(walk_multi_emit_kernel, dim3(m.nblocks > lanes ? m.nblocks : lanes), dim3(WG), 0, s, m);
+        hipLaunchKernelGGL(records ? records_multi_table_kernel : walk_multi_table_kernel, dim3(m.nblocks), dim3(WG),
+                           0, s, m);
+    hipLaunchKernelGGL(records ? records_multi_chain_kernel : walk_multi_chain_kernel, dim3(lanes), dim3(WG), 0, s, m);
+    hipLaunchKernelGGL(records ? records_multi_scan_kernel : walk_multi_scan_kernel, dim3(1), dim3(WG), 0, s, m);
+    hipLaunchKernelGGL(records ? records_multi_emit_kernel : walk_multi_emit_kernel,
+                       dim3(m.nblocks > lanes ? m.nblocks : lanes), dim3(WG), 0, s, m);
     return hipGetLastError() == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
+}
+
+/* The many-image call of either family (m: arena, outputs, rows and totals
+ * set): geometry and scratch pointers from the plan, the descriptors staged,
+ * the four launches. */
+int walk_multi(MWalk &m, const Plan &p, const zscrc_walk_image *images, size_t k, void *scratch,
+               const zscrc_walk_opts *opts, hipStream_t s, bool records)
+{
+    m.k = (uint32_t)k;
+    m.nblocks = (uint32_t)p.nblocks;
+    m.bs = p.bs;
+    m.ts = p.ts;
+    m.rounds = p.rounds;
+    return zs::with_scratch(scratch, p.bytes, true, s, [&](void *sp, Scratch *sc) {
+        uint8_t *base = static_cast<uint8_t *>(sp);
+        m.im = reinterpret_cast<const ImgD *>(base);
+        m.tail_n = reinterpret_cast<uint64_t *>(base + p.tail_at);
+        m.entry = reinterpret_cast<Entry *>(base + p.entry_at);
+        m.J = reinterpret_cast<uint32_t *>(base + p.j_at);
+        m.C = reinterpret_cast<uint32_t *>(base + p.c_at);
+        const int rc = stage_descriptors(*sc, images, k, opts, base, s);
+        return rc ? rc : launch_multi(m, s, records);
+    });
 }
 
 } /* namespace */
@@ -1279,30 +1383,38 @@ int zscrc_device_walk_multi(const void *d_arena, uint64_t arena_size, const zscr
     if (!d_arena || !d_rows || !d_tot || (cap && (!d_span_off || !d_span_len || !d_span_img)) || flags ||
         (reinterpret_cast<uintptr_t>(scratch) & 15) || !plan_multi(images, k, true, arena_size, opts, &p, nullptr))
         return ZSCRC_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     MWalk m{};
     m.arena = static_cast<const uint8_t *>(d_arena);
-    m.k = (uint32_t)k;
-    m.nblocks = (uint32_t)p.nblocks;
-    m.bs = p.bs;
-    m.ts = p.ts;
-    m.rounds = p.rounds;
     m.off = d_span_off;
     m.len = d_span_len;
     m.img = d_span_img;
     m.cap = cap;
     m.rows = d_rows;
     m.tot = d_tot;
-    return zs::with_scratch(scratch, p.bytes, true, s, [&](void *sp, Scratch *sc) {
-        uint8_t *base = static_cast<uint8_t *>(sp);
-        m.im = reinterpret_cast<const ImgD *>(base);
-        m.tail_n = reinterpret_cast<uint64_t *>(base + p.tail_at);
-        m.entry = reinterpret_cast<Entry *>(base + p.entry_at);
-        m.J = reinterpret_cast<uint32_t *>(base + p.j_at);
-        m.C = reinterpret_cast<uint32_t *>(base + p.c_at);
-        const int rc = stage_descriptors(*sc, images, k, opts, base, s);
-        return rc ? rc : launch_multi(m, s);
-    });
+    return walk_multi(m, p, images, k, scratch, opts, static_cast<hipStream_t>(stream), false);
+}
+
+size_t zscrc_device_records_multi_scratch_bytes(const zscrc_walk_image *images, size_t k,
+                                                const zscrc_walk_opts *opts)
+{
+    return zscrc_device_walk_multi_scratch_bytes(images, k, opts);
+}
+
+int zscrc_device_records_multi(const void *d_arena, uint64_t arena_size, const zscrc_walk_image *images, size_t k,
+                               struct zscrc_zs_record *d_recs, size_t cap, uint64_t *d_rows, uint64_t *d_tot,
+                               void *scratch, const zscrc_walk_opts *opts, unsigned flags, void *stream)
+{
+    Plan p;
+    if (!d_arena || !d_rows || !d_tot || (cap && !d_recs) || flags || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
+        !plan_multi(images, k, true, arena_size, opts, &p, nullptr))
+        return ZSCRC_EINVAL;
+    MWalk m{};
+    m.arena = static_cast<const uint8_t *>(d_arena);
+    m.off = reinterpret_cast<uint64_t *>(d_recs); /* four words an entry (RecordList) */
+    m.cap = cap;
+    m.rows = d_rows;
+    m.tot = d_tot;
+    return walk_multi(m, p, images, k, scratch, opts, static_cast<hipStream_t>(stream), true);
 }
 
 int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size, const zscrc_walk_image *images, size_t k,

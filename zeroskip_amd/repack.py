@@ -287,24 +287,37 @@ def device_merge(d_src, lists, drop_deletes: bool = False, out=None, tile_record
 
 def device_repack(d_arena, images, kinds, uuid: bytes, startidx: int, endidx: int, drop_deletes: bool):
     """A repack of device-resident file images without an image byte or a key
-    crossing PCIe: zsfile.device_records per image, device_merge,
-    device_pack -> (file, report).  images: (offset, size) pairs into the
+    crossing PCIe: the record lists (one zsfile.device_records_multi call
+    when every image is active or finalised, else zsfile.device_records per
+    image), device_merge, device_pack -> (file, report).  images: (offset, size) pairs into the
     uint8 device tensor d_arena in load order (branch 1 of zsdb_repack: the
     finalised files oldest first, drop_deletes False; branch 2: the newer
     packed file first and the older last, drop_deletes True); kinds: each
     image's zsfile kind.  file: the packed file as a uint8 device tensor.
     report: records_in, records_out, superseded, deletes_dropped, file_bytes
-    and pack (device_pack's result words as a list).  The host reads each
-    image's record count, the winners' count and the file's size."""
+    and pack (device_pack's result words as a list).  The host reads the
+    lister's totals (per image: its record count, only where a packed file is
+    among them), the winners' count and the file's size."""
     from . import zsfile
 
+    images, kinds = list(images), list(kinds)
     lists = []
-    for (off, size), kind in zip(images, kinds):
-        recs, res = zsfile.device_records(d_arena[off:off + size], kind)
-        code, n = (int(v) for v in res[:2].cpu())
-        if code not in (0, zsfile.END):
-            raise ValueError("image at %d does not list: code %d" % (off, code))
-        lists.append((recs[:n], off))
+    if images and all(kind in (zsfile.ACTIVE, zsfile.FINALISED) for kind in kinds):
+        # every image has a chain: one call lists them all as one list over the arena
+        recs, rows, tot = zsfile.device_records_multi(d_arena, images)
+        t = [int(v) for v in tot.cpu()]
+        if t[7]:
+            for (off, _), row in zip(images, rows[:, 0].cpu().tolist()):
+                if row != zsfile.END:
+                    raise ValueError("image at %d does not list: code %d" % (off, row))
+        lists.append((recs[:t[1]], 0))
+    else:
+        for (off, size), kind in zip(images, kinds):
+            recs, res = zsfile.device_records(d_arena[off:off + size], kind)
+            code, n = (int(v) for v in res[:2].cpu())
+            if code not in (0, zsfile.END):
+                raise ValueError("image at %d does not list: code %d" % (off, code))
+            lists.append((recs[:n], off))
     import torch
 
     # room for every record in: one merge, no sizing call

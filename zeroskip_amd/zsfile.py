@@ -243,6 +243,56 @@ def device_walk_multi(d_arena: torch.Tensor, images, cap: int | None = None, blo
     return off, ln, img, rows, tot
 
 
+RECORDS_ROW_WORDS = 12  # ZSCRC_RECORDS_ROW_WORDS
+RECORDS_TOT_WORDS = 8  # ZSCRC_RECORDS_TOT_WORDS
+
+
+def records_multi_scratch_bytes(images, block_bytes: int = 0, tile_bytes: int = 0) -> int:
+    """zscrc_device_records_multi_scratch_bytes for images = [(off, size)];
+    0 = bad arguments."""
+    arr, k = _walk_images(images)
+    return lib().zscrc_device_records_multi_scratch_bytes(arr, k, ctypes.byref(WalkOpts(block_bytes, tile_bytes)))
+
+
+def device_records_multi(d_arena: torch.Tensor, images, cap: int | None = None, block_bytes: int = 0,
+                         tile_bytes: int = 0, out: tuple | None = None, scratch: torch.Tensor | None = None):
+    """The records of the k active or finalised images [(off, size)] of a
+    device-resident arena, listed in one call (zscrc_device_records_multi),
+    asynchronous on the current stream: (recs, rows, tot) int64 device
+    tensors.  recs is [cap, 4] (default cap: the sum of size // 24 + 1, what
+    device_records takes per image) of which the first min(tot[1], cap) rows
+    are written: image 0's records, then image 1's ..., key_off and val_off
+    (unless DELETED) as offsets into the arena -- one list with base 0 for
+    repack.device_merge, and one repack.device_pack takes as it is.  rows (k,
+    12), image-relative: device_records' res of that image alone with
+    unlimited room (the code is never OVERFLOW; -1 for an image of fewer than
+    40 bytes), [9] the index of its first record in recs.  tot: [OVERFLOW or
+    0, records of all images, deletes, sum of key lengths, sum of value
+    lengths, longest key, longest value, images whose code is not END].
+    out: preallocated (recs, rows, tot); scratch: a 16-byte aligned uint8
+    tensor of records_multi_scratch_bytes() bytes (default: the library's
+    own, stream-ordered)."""
+    size = d_arena.numel() * d_arena.element_size()
+    dev = d_arena.device
+    arr, k = _walk_images(images)
+    if cap is None:
+        cap = sum(arr[j].size // 24 + 1 for j in range(k))
+    if out is None:
+        out = (torch.empty((max(cap, 1), 4), dtype=torch.int64, device=dev),
+               torch.empty((max(k, 1), RECORDS_ROW_WORDS), dtype=torch.int64, device=dev),
+               torch.empty(RECORDS_TOT_WORDS, dtype=torch.int64, device=dev))
+    recs, rows, tot = out
+    assert recs.numel() >= 4 * cap
+    assert rows.numel() >= k * RECORDS_ROW_WORDS and tot.numel() >= RECORDS_TOT_WORDS
+    opts = WalkOpts(block_bytes, tile_bytes)
+    with torch.cuda.device(dev):
+        check(lib().zscrc_device_records_multi(
+            d_arena.data_ptr(), size, arr, k, recs.data_ptr() if recs.numel() else None, cap, rows.data_ptr(),
+            tot.data_ptr(), None if scratch is None else scratch.data_ptr(), ctypes.byref(opts), 0,
+            torch.cuda.current_stream(dev).cuda_stream), "zscrc_device_records_multi")
+    return recs, rows, tot
+
+
 def verify_device_images(d_arena: torch.Tensor, images) -> list:
     """verify_device_image() for the k active or finalised images [(off,
     size)] of a device-resident arena in one call (zscrc_device_verify_images):
