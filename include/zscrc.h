@@ -805,6 +805,101 @@ int zscrc_device_merge(const void *d_src, uint64_t src_size,
                        struct zscrc_zs_record *d_out, size_t cap, uint64_t *d_res,
                        void *scratch, const zscrc_merge_opts *opts, unsigned flags, void *stream);
 
+/* The lookup on the device: the read path for record lists that live in device
+ * memory -- a batch of keys looked up in k sorted lists over one d_src, without
+ * a key or a list crossing PCIe.  (The reference reads by a binary search over
+ * a packed file's pointer section, zs_packed_file_bsearch_index,
+ * src/zeroskip-packed.c:558-615, which zsdb_fetch, src/zeroskip.c:1042-1173,
+ * calls over the packed files newest first.)
+ * Levels: `levels` is a HOST array of k <= ZSCRC_FIND_LEVELS_MAX lists over the
+ * one d_src, in priority order; it reaches the device through the library's
+ * pinned staging, as the merge's descriptors do.  Each list is what
+ * zscrc_device_merge writes, or what zscrc_device_records writes for a PACKED
+ * image: its keys strictly ascending in the merge's order (memcmp_raw).  base
+ * is added to key_off, and to val_off unless that is ZSCRC_ZS_DELETED; the
+ * sequence number of record j of level l is the merge's, seq = n_0 + .. +
+ * n_(l-1) + j.  Empty levels are legal, and so is k = 0.
+ * Queries: query i is the key d_qsrc[key_off, +key_len) of d_queries[i]; the
+ * value words are never read, so a record list of another image is a query
+ * list as it stands.  A query whose key does not lie inside [0, qsrc_size)
+ * (checked against the bytes left, never with an add that can wrap) gets level
+ * = ZSCRC_FIND_BAD_QUERY and the other three words 0; no other query is
+ * affected.
+ * Hit i: the levels are searched in order and the first one that holds the key
+ * ends the search: level = l, location = the index in level l, val_off rebased
+ * (or ZSCRC_ZS_DELETED), val_len as the record has it.  A delete is a hit: the
+ * key is deleted and older levels are not consulted -- deliberately not
+ * zsdb_fetch's behaviour, which hands a delete record out as a value; the
+ * caller sees ZSCRC_ZS_DELETED and decides.  When no level holds the key, level
+ * = ZSCRC_FIND_NONE, location = the lower bound in the LAST level (the number
+ * of its keys smaller than the query; 0 for k = 0) and val_off = val_len = 0:
+ * for k = 1 location is exactly *location of zs_packed_file_bsearch_index,
+ * found or not.  Where a level holds a key twice (a violated precondition),
+ * location is the first of them.
+ * Launches in stream order (one thread a level record: rebase, check, with
+ * CHECK_ORDER its key against its predecessor's; the splitter tables; one
+ * search launch per level that is not empty, persistent workgroups with a
+ * grid-stride loop over the queries; one lane that seals the result words);
+ * every grid is sized on the host from n_total, k and nq, no workgroup waits
+ * for another.  splitters: S records of every level at evenly spaced positions
+ * are sampled into a table (rebased offset, length, the key's words at 0 and
+ * 8) that a workgroup copies into LDS; a query is narrowed to a bucket by
+ * bisection there and the bisection finished against the records.  A power of
+ * two, 2 <= S <= 2048 (64 KiB of LDS), or 1 for no table (plain bisection); 0 =
+ * the default (1024).
+ * Limits: n_total and nq <= 2^31 - 1, k <= 64, src_size and qsrc_size <= 2^62. */
+typedef struct zscrc_find_hit { uint64_t level, location, val_off, val_len; } zscrc_find_hit;
+typedef struct zscrc_find_opts { uint32_t splitters; } zscrc_find_opts;   /* NULL / 0 = default */
+#define ZSCRC_FIND_NONE        UINT64_MAX
+#define ZSCRC_FIND_BAD_QUERY   (UINT64_MAX - 1)
+#define ZSCRC_FIND_CHECK_ORDER 1u
+#define ZSCRC_FIND_LEVELS_MAX  64
+#define ZSCRC_FIND_RES_WORDS   8
+/* Bytes of scratch zscrc_device_find needs for k levels: 32 bytes a level and
+ * a few words, and 32 * splitters a level where there is a table; a multiple
+ * of 16, monotone in k.  0 = a bad option or k above the limit. */
+size_t zscrc_device_find_scratch_bytes(size_t k, const zscrc_find_opts *opts);
+/* Asynchronous on `stream`: nothing is copied to the host, nothing waits.
+ * d_hits (device, nq entries).  d_res (device, ZSCRC_FIND_RES_WORDS words):
+ *   [0] 0; (uint64_t)(int64_t)ZSCRC_EINVAL = some rebased level record does not
+ *       lie inside [0, src_size) (zscrc_device_merge's check), or, with
+ *       ZSCRC_FIND_CHECK_ORDER, some record's key is not greater than its
+ *       predecessor's in the same level (never across a level boundary): then
+ *       no hit is written at all
+ *   [1] nq; on EINVAL the smallest offending seq, bounds offences taking
+ *       precedence over order offences
+ *   [2] hits with a value  [3] hits that are deletes  [4] queries not found
+ *   [5] bad queries: [2] + [3] + [4] + [5] == nq whenever [0] == 0
+ *   [6] the sum of val_len over [2], modulo 2^64: what a value gather sizes its
+ *       output by
+ *   [7] 1 if the EINVAL is an order offence, else 0
+ * Every level record is bounds-checked on every call, whatever the queries
+ * touch; the results do not depend on `opts` nor on which records the search
+ * happens to visit.  Counts and sums are integer atomics only: two runs are bit
+ * for bit equal.  Without CHECK_ORDER a level that does not ascend is searched
+ * all the same, inside its bounds, and the hits are unspecified.
+ * scratch: 16-byte aligned device memory of zscrc_device_find_scratch_bytes
+ * bytes, or NULL for the walk's per-device library scratch (zscrc_device_walk:
+ * stream-ordered between calls, kept until zscrc_release_cache).
+ * ZSCRC_EINVAL before any device call: d_res NULL; nq > 0 with d_queries or
+ * d_hits NULL; k > 0 with levels NULL; k > 64; a level with n > 0 and d_recs
+ * NULL; d_src NULL with src_size > 0, and likewise d_qsrc; src_size or
+ * qsrc_size > 2^62; n_total or nq > 2^31 - 1; scratch not 16-byte aligned; an
+ * unknown flag; a bad option. */
+int zscrc_device_find(const void *d_src, uint64_t src_size,
+                      const zscrc_merge_list *levels, size_t k,
+                      const void *d_qsrc, uint64_t qsrc_size,
+                      const struct zscrc_zs_record *d_queries, size_t nq,
+                      zscrc_find_hit *d_hits, uint64_t *d_res, void *scratch,
+                      const zscrc_find_opts *opts, unsigned flags, void *stream);
+/* The same search for lists and keys in host memory, one thread, no device:
+ * the same words for the same bytes (hits, res, CHECK_ORDER included), computed
+ * through the same inline functions as the kernels.  The argument checks are
+ * zscrc_device_find's without scratch and options. */
+int zscrc_zs_find(const void *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k,
+                  const void *qsrc, uint64_t qsrc_size, const struct zscrc_zs_record *queries, size_t nq,
+                  zscrc_find_hit *hits, uint64_t res[ZSCRC_FIND_RES_WORDS], unsigned flags);
+
 /* `consistent` for one process / one GPU (zsdb_consistent,
  * src/zeroskip.c:1399-1407, and tool/cmd-consistent.c:23-49 are stubs in the
  * reference): every .zsdb / header / commit CRC of the DB directory,

@@ -114,6 +114,9 @@ SIGNATURES = {
                                  _vp]),
     "zscrc_device_merge_scratch_bytes": (_sz, [_sz, _vp]),
     "zscrc_device_merge": (_int, [_vp, _u64, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.c_uint, _vp]),
+    "zscrc_device_find_scratch_bytes": (_sz, [_sz, _vp]),
+    "zscrc_device_find": (_int, [_vp, _u64, _vp, _sz, _vp, _u64, _vp, _sz, _vp, _vp, _vp, _vp, ctypes.c_uint, _vp]),
+    "zscrc_zs_find": (_int, [_vp, _u64, _vp, _sz, _vp, _u64, _vp, _sz, _vp, _vp, ctypes.c_uint]),
 }
 ABI_VERSION = 4  # include/zscrc.h ZSCRC_ABI_VERSION
 

@@ -293,6 +293,104 @@ def device_records_multi(d_arena: torch.Tensor, images, cap: int | None = None, 
     return recs, rows, tot
 
 
+class FindOpts(ctypes.Structure):
+    """zscrc_find_opts (include/zscrc.h); 0 = the default."""
+    _fields_ = [("splitters", ctypes.c_uint32)]
+
+
+FIND_RES_WORDS = 8  # ZSCRC_FIND_RES_WORDS
+FIND_NONE = -1  # ZSCRC_FIND_NONE as the int64 a hit row holds
+FIND_BAD_QUERY = -2  # ZSCRC_FIND_BAD_QUERY
+FIND_CHECK_ORDER = 1  # ZSCRC_FIND_CHECK_ORDER
+FIND_LEVELS_MAX = 64  # ZSCRC_FIND_LEVELS_MAX
+FIND_DEFAULT_SPLITTERS = 1024  # zscrc_find.hip DEF_SPLITTERS: what splitters = 0 means
+FIND_GRID_THREADS = 1024 * 256  # zscrc_find.hip GRID_MAX * WG: the search's persistent grid at its largest
+
+
+def _find_levels(levels, ptr):
+    """[(recs, base)] as a zscrc_merge_list array (one entry's room for none);
+    ptr(recs): the address of a list's first record."""
+    from .repack import MergeList
+
+    levels = list(levels)
+    arr = (MergeList * max(len(levels), 1))()
+    for j, (recs, base) in enumerate(levels):
+        n = int(recs.shape[0])
+        assert recs.ndim == 2 and (n == 0 or recs.shape[1] == 4)
+        arr[j].d_recs, arr[j].n, arr[j].base = (ptr(recs) if n else None), n, base
+    return arr, len(levels)
+
+
+def device_find_scratch_bytes(k: int, splitters: int = 0) -> int:
+    """zscrc_device_find_scratch_bytes; 0 = a bad option or too many levels."""
+    return lib().zscrc_device_find_scratch_bytes(k, ctypes.byref(FindOpts(splitters)))
+
+
+def device_find(d_src: torch.Tensor, levels, d_qsrc: torch.Tensor, queries: torch.Tensor, check_order: bool = False,
+                splitters: int = 0, out: tuple | None = None, scratch: torch.Tensor | None = None):
+    """A batch of keys looked up in device-resident sorted record lists on the
+    GPU (zscrc_device_find), asynchronous on the current stream: (hits, res)
+    int64 device tensors.  d_src: the uint8 device tensor the levels' rebased
+    offsets point into; levels: a sequence of (recs, base) in priority order,
+    recs an int64 [n, 4] device tensor such as repack.device_merge returns or
+    device_records gives for a packed image, sliced to its count, its keys
+    strictly ascending; d_qsrc: the uint8 device tensor the queries' keys lie
+    in; queries: int64 [nq, 4], of which key_off and key_len are read (a
+    record list is a query list).  hits [nq, 4]: level (FIND_NONE: no level
+    holds the key, FIND_BAD_QUERY: the key lies outside d_qsrc), location (the
+    index in that level; not found: the lower bound in the last level),
+    val_off rebased or DELETED (a delete is a hit of the first level that
+    holds the key), val_len.  res: [code (0, -1 a level record outside d_src
+    or, with check_order, a key not above its predecessor's: no hit written),
+    nq or the first offending sequence number, hits with a value, deleted,
+    not found, bad queries, sum of the values' lengths, 1 = an order
+    offence].  splitters: the records sampled per level into the LDS table, a
+    power of two up to 2048, 1 = plain bisection, 0 = the default; the result
+    never depends on it.  out: preallocated (hits, res); scratch: a 16-byte
+    aligned uint8 tensor of device_find_scratch_bytes(k) bytes (default: the
+    library's own, stream-ordered)."""
+    dev = d_src.device
+    arr, k = _find_levels(levels, lambda r: r.data_ptr())
+    for recs, _ in levels:
+        assert recs.dtype == torch.int64 and recs.is_contiguous()
+    nq = int(queries.shape[0])
+    assert queries.dtype == torch.int64 and queries.is_contiguous() and (nq == 0 or queries.shape[1] == 4)
+    if out is None:
+        out = (torch.empty((nq, 4), dtype=torch.int64, device=dev),
+               torch.empty(FIND_RES_WORDS, dtype=torch.int64, device=dev))
+    hits, res = out
+    assert hits.numel() >= 4 * nq and res.numel() >= FIND_RES_WORDS
+    src_bytes = d_src.numel() * d_src.element_size()
+    q_bytes = d_qsrc.numel() * d_qsrc.element_size()
+    opts = FindOpts(splitters)
+    with torch.cuda.device(dev):
+        check(lib().zscrc_device_find(
+            d_src.data_ptr() if src_bytes else None, src_bytes, arr, k, d_qsrc.data_ptr() if q_bytes else None,
+            q_bytes, queries.data_ptr() if nq else None, nq, hits.data_ptr() if nq else None, res.data_ptr(),
+            None if scratch is None else scratch.data_ptr(), ctypes.byref(opts),
+            FIND_CHECK_ORDER if check_order else 0, torch.cuda.current_stream(dev).cuda_stream), "zscrc_device_find")
+    return hits, res
+
+
+def find(src, levels, qsrc, queries, check_order: bool = False):
+    """device_find for lists and keys in host memory (zscrc_zs_find, one
+    thread, no device): (hits int64 [nq, 4], res int64 [8]) numpy arrays, the
+    same words for the same bytes.  src, qsrc: bytes or uint8 arrays; levels:
+    (recs, base) with recs [n, 4] uint64 or int64 arrays; queries [nq, 4]."""
+    s, sp, sn = _host(src)
+    q, qp, qn = _host(qsrc)
+    levels = [(np.ascontiguousarray(r).view(np.int64).reshape(-1, 4), b) for r, b in levels]
+    arr, k = _find_levels(levels, lambda r: r.ctypes.data)
+    qr = np.ascontiguousarray(queries).view(np.int64).reshape(-1, 4)
+    nq = len(qr)
+    hits = np.empty((nq, 4), np.int64)
+    res = np.empty(FIND_RES_WORDS, np.int64)
+    check(lib().zscrc_zs_find(sp if sn else None, sn, arr, k, qp if qn else None, qn, qr.ctypes.data if nq else None,
+                              nq, hits.ctypes.data if nq else None, res.ctypes.data,
+                              FIND_CHECK_ORDER if check_order else 0), "zscrc_zs_find")
+    return hits, res
+
+
 def verify_device_images(d_arena: torch.Tensor, images) -> list:
     """verify_device_image() for the k active or finalised images [(off,
     size)] of a device-resident arena in one call (zscrc_device_verify_images):
