@@ -900,6 +900,72 @@ int zscrc_zs_find(const void *src, uint64_t src_size, const zscrc_merge_list *le
                   const void *qsrc, uint64_t qsrc_size, const struct zscrc_zs_record *queries, size_t nq,
                   zscrc_find_hit *hits, uint64_t res[ZSCRC_FIND_RES_WORDS], unsigned flags);
 
+/* The value gather on the device: the values a batch of hits names, copied out
+ * of d_src into one dense buffer -- find, then gather, is a multi-get (what a
+ * user of the reference calls zsdb_fetch, src/zeroskip.c:1042-1173, for) that
+ * answers without a key, a list or a value crossing PCIe except the answer.
+ * Items: d_items has nq entries of four words, of which words 0, 2 and 3 are
+ * read.  An item carries a value when word 0 is below ZSCRC_FIND_BAD_QUERY and
+ * word 2 is not ZSCRC_ZS_DELETED; its value is d_src[val_off, +val_len).  So
+ * the hits of zscrc_device_find are a gather list as they stand -- and so is a
+ * record list: zscrc_zs_record has val_off and val_len in the same two words
+ * and a key_off never reaches 2^62, so every record that is not a delete gives
+ * its value.  Every value-carrying item is checked against src_size on every
+ * call (against the bytes left, never with an add that can wrap): stale or
+ * garbage hits never make a kernel read outside the source.
+ * Outputs: d_out (16-byte aligned, out_cap bytes) receives the values back to
+ * back in item order, no padding; d_offs (nq + 1 words) the start of every
+ * item's value in d_out and, in d_offs[nq], the total -- the CSR layout of a
+ * jagged tensor; an item without a value has length 0.  d_crcs (nq words, or
+ * NULL): d_crcs[i] = crc32c(0, value i), computed over the gathered bytes in
+ * d_out by the library's variable-length batch, so it checks the copy end to
+ * end; 0 for an empty item.  The copy writes the bytes [0, total) of d_out and
+ * no other.
+ * d_res (device, ZSCRC_GATHER_RES_WORDS words):
+ *   [0] 0; ZSCRC_ZS_OVERFLOW = total > out_cap: no byte of d_out is written,
+ *       d_offs is written in full (out_cap 0 with d_out NULL is the sizing
+ *       call, which leaves d_crcs alone);
+ *       (uint64_t)(int64_t)ZSCRC_EINVAL = some value does not lie inside
+ *       [0, src_size): nothing of d_out or d_offs is written.
+ *       On any code but 0 outside the sizing call every d_crcs[i] is 0.
+ *   [1] nq; on EINVAL the smallest offending index
+ *   [2] items with a value  [3] total bytes (a sum that saturates at
+ *   UINT64_MAX)  [4] deletes  [5] not found  [6] bad queries  [7] the longest
+ *   value: [2] + [4] + [5] + [6] == nq whenever [0] is 0 or OVERFLOW; on
+ *   EINVAL [2..7] are 0.  After a find with code 0 the gather's [2], [3], [4],
+ *   [5], [6] equal the find's [2], [6], [3], [4], [5].
+ * Counts are integer atomics and workgroup sums only: two runs are bit for bit
+ * equal.  Launches in stream order (size and check; one workgroup's scan;
+ * offsets; the copy, which cuts the output into tiles of tile_bytes -- a power
+ * of two, 64 .. 65536, 0 = the default, never changing the result -- and
+ * works through a run of them in chunks of a fixed number of staged offsets,
+ * however many items reach into a tile; the CRC batch); every grid is sized on
+ * the host from nq and out_cap, no workgroup waits for another, nothing is
+ * copied to the host.
+ * scratch: 16-byte aligned device memory of zscrc_device_gather_scratch_bytes
+ * bytes (a few words, 8 bytes per 1,024 items, and 16 bytes an item for the
+ * CRC batch's descriptors; a multiple of 16, monotone in nq; 0 = a bad option
+ * or nq above the limit), or NULL for the per-device library scratch.
+ * ZSCRC_EINVAL before any device call: d_res or d_offs NULL; nq > 0 with
+ * d_items NULL; d_src NULL with src_size > 0; out_cap > 0 with d_out NULL;
+ * d_out or scratch not 16-byte aligned; d_out overlapping d_src; any flag
+ * (none is defined); a bad tile; nq > 2^31 - 1; src_size > 2^62. */
+typedef struct zscrc_gather_opts { uint64_t tile_bytes; } zscrc_gather_opts;   /* NULL / 0 = default */
+#define ZSCRC_GATHER_RES_WORDS 8
+size_t zscrc_device_gather_scratch_bytes(size_t nq, const zscrc_gather_opts *opts);
+int zscrc_device_gather(const void *d_src, uint64_t src_size,
+                        const zscrc_find_hit *d_items, size_t nq,
+                        void *d_out, uint64_t out_cap, uint64_t *d_offs, uint32_t *d_crcs,
+                        uint64_t *d_res, void *scratch, const zscrc_gather_opts *opts,
+                        unsigned flags, void *stream);
+/* The same gather in host memory, one thread, no device: the same words for
+ * the same bytes (out, offs, crcs, res), built through the same inline
+ * functions as the kernels.  The argument checks are zscrc_device_gather's
+ * without scratch, options, flags and alignment. */
+int zscrc_zs_gather(const void *src, uint64_t src_size, const zscrc_find_hit *items, size_t nq,
+                    void *out, uint64_t out_cap, uint64_t *offs, uint32_t *crcs,
+                    uint64_t res[ZSCRC_GATHER_RES_WORDS]);
+
 /* `consistent` for one process / one GPU (zsdb_consistent,
  * src/zeroskip.c:1399-1407, and tool/cmd-consistent.c:23-49 are stubs in the
  * reference): every .zsdb / header / commit CRC of the DB directory,

@@ -391,6 +391,124 @@ def find(src, levels, qsrc, queries, check_order: bool = False):
     return hits, res
 
 
+class GatherOpts(ctypes.Structure):
+    """zscrc_gather_opts (include/zscrc.h); 0 = the default."""
+    _fields_ = [("tile_bytes", ctypes.c_uint64)]
+
+
+GATHER_RES_WORDS = 8  # ZSCRC_GATHER_RES_WORDS
+GATHER_DEFAULT_TILE = 16384  # zscrc_gather.hip DEF_TILE: what tile_bytes = 0 means
+GATHER_STAGE = 1024  # zscrc_gather.hip STAGE: the starts a chunk of the copy stages in LDS
+
+
+def device_gather_scratch_bytes(nq: int, tile_bytes: int = 0) -> int:
+    """zscrc_device_gather_scratch_bytes; 0 = a bad tile or too many items."""
+    return lib().zscrc_device_gather_scratch_bytes(nq, ctypes.byref(GatherOpts(tile_bytes)))
+
+
+def device_gather(d_src: torch.Tensor, items: torch.Tensor, cap: int | None = None, crcs: bool = False,
+                  tile_bytes: int = 0, out: tuple | None = None, scratch: torch.Tensor | None = None):
+    """The values a batch of hits names, copied out of d_src into one dense
+    device buffer on the GPU (zscrc_device_gather): (values uint8, offs int64
+    [nq + 1], crcs uint32-as-int32 [nq] or None, res int64 [8]) device tensors.
+    items: int64 [nq, 4], device_find's hits or a record list (words 0, 2 and
+    3 are read: a row carries a value unless word 0 is FIND_NONE or
+    FIND_BAD_QUERY or word 2 is DELETED).  Value i is values[offs[i]:offs[i +
+    1]], offs[nq] the total: the CSR layout of a jagged tensor.  With cap (the
+    bytes of the values buffer) the call is asynchronous on the current
+    stream; cap=None makes the sizing call first, reads the one total word
+    and allocates.  res: [code (0; 3 = the total exceeds cap: no value byte
+    written, offs complete; -1 = a value outside d_src: nothing written), nq
+    or the first offending index, items with a value, total bytes, deletes,
+    not found, bad queries, the longest value].  crcs: crc32c(0, value i) over
+    the gathered bytes.  tile_bytes: the copy's output tile, a power of two 64
+    .. 65536, 0 = the default; the result never depends on it.  out:
+    preallocated (values, offs, crcs | None, res), values 16-byte aligned;
+    scratch: a 16-byte aligned uint8 tensor of device_gather_scratch_bytes(nq)
+    bytes (default: the library's own, stream-ordered)."""
+    dev = d_src.device
+    nq = int(items.shape[0])
+    assert items.dtype == torch.int64 and items.is_contiguous() and (nq == 0 or items.shape[1] == 4)
+    src_bytes = d_src.numel() * d_src.element_size()
+    opts = GatherOpts(tile_bytes)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    sp = None if scratch is None else scratch.data_ptr()
+
+    def call(values, vcap, offs, crc, res):
+        with torch.cuda.device(dev):
+            check(lib().zscrc_device_gather(
+                d_src.data_ptr() if src_bytes else None, src_bytes, items.data_ptr() if nq else None, nq,
+                values.data_ptr() if values is not None and values.numel() else None, vcap, offs.data_ptr(),
+                None if crc is None else crc.data_ptr(), res.data_ptr(), sp, ctypes.byref(opts), 0, stream),
+                "zscrc_device_gather")
+
+    if out is not None:
+        values, offs, crc, res = out
+        assert offs.numel() >= nq + 1 and res.numel() >= GATHER_RES_WORDS and (crc is None or crc.numel() >= nq)
+        call(values, values.numel() if cap is None else cap, offs, crc, res)
+        return values, offs, crc, res
+    offs = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+    res = torch.empty(GATHER_RES_WORDS, dtype=torch.int64, device=dev)
+    if cap is None:
+        call(None, 0, offs, None, res)
+        code, total = (int(v) for v in res[[0, 3]].cpu())
+        if code == -1:
+            return torch.empty(0, dtype=torch.uint8, device=dev), offs, None, res
+        cap = total
+    values = torch.empty(cap, dtype=torch.uint8, device=dev)
+    crc = torch.zeros(nq, dtype=torch.int32, device=dev) if crcs else None  # a total of 0 is a sizing call
+    call(values, cap, offs, crc, res)
+    return values, offs, crc, res
+
+
+def gather(src, items, crcs: bool = False, cap: int | None = None):
+    """device_gather in host memory (zscrc_zs_gather, one thread, no device):
+    (values uint8, offs int64 [nq + 1], crcs uint32 [nq] or None, res int64
+    [8]) numpy arrays, the same words for the same bytes.  src: bytes or a
+    uint8 array; items [nq, 4] uint64 or int64.  cap: the bytes of the values
+    buffer (default: a sizing call first)."""
+    s, sp, sn = _host(src)
+    it = np.ascontiguousarray(items).view(np.int64).reshape(-1, 4)
+    nq = len(it)
+    offs = np.empty(nq + 1, np.int64)
+    res = np.empty(GATHER_RES_WORDS, np.int64)
+
+    def call(values, vcap, crc):
+        check(lib().zscrc_zs_gather(sp if sn else None, sn, it.ctypes.data if nq else None, nq,
+                                    values.ctypes.data if values is not None and vcap else None, vcap,
+                                    offs.ctypes.data, None if crc is None else crc.ctypes.data, res.ctypes.data),
+              "zscrc_zs_gather")
+
+    if cap is None:
+        call(None, 0, None)
+        if int(res[0]) == -1:
+            return np.empty(0, np.uint8), offs, None, res
+        cap = int(res[3])
+    values = np.empty(cap, np.uint8)
+    crc = np.zeros(nq, np.uint32) if crcs else None
+    call(values, cap, crc)
+    return values, offs, crc, res
+
+
+def device_get(d_src: torch.Tensor, levels, d_qsrc: torch.Tensor, queries: torch.Tensor, cap: int | None = None,
+               crcs: bool = False, check_order: bool = False, splitters: int = 0, tile_bytes: int = 0):
+    """A multi-get on the GPU: device_find, then device_gather over its hits,
+    in one call: (values, offs, crcs | None, hits, find_res, gather_res).
+    With cap the two stages are asynchronous on the current stream; otherwise
+    the values buffer is sized from the find's res[6], the sum of the found
+    values' lengths -- one 8-byte read.  A find that refuses its levels
+    (find_res[0] = -1) leaves the hits unwritten; the gather is then not
+    run and values, offs, crcs and gather_res are None."""
+    hits, fres = device_find(d_src, levels, d_qsrc, queries, check_order=check_order, splitters=splitters)
+    if cap is None:
+        code, total = (int(v) for v in fres[[0, 6]].cpu())
+        if code != 0:
+            return None, None, None, hits, fres, None
+        cap = total
+    values, offs, crc, gres = device_gather(d_src, hits, cap=cap, crcs=crcs, tile_bytes=tile_bytes)
+    return values, offs, crc, hits, fres, gres
+
+
 def verify_device_images(d_arena: torch.Tensor, images) -> list:
     """verify_device_image() for the k active or finalised images [(off,
     size)] of a device-resident arena in one call (zscrc_device_verify_images):
