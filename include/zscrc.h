@@ -966,6 +966,115 @@ int zscrc_zs_gather(const void *src, uint64_t src_size, const zscrc_find_hit *it
                     void *out, uint64_t out_cap, uint64_t *offs, uint32_t *crcs,
                     uint64_t res[ZSCRC_GATHER_RES_WORDS]);
 
+/* The prefix scan on the device: ordered iteration over record lists that live
+ * in device memory -- for every prefix of a batch, the keys of k sorted lists
+ * that begin with it, in key order, each key once, from the newest list that
+ * holds it, deleted keys skipped.  (The reference's zsdb_foreach(db, prefix,
+ * ...), src/zeroskip.c:1681-1823, walks all files newest first in key order
+ * this way and stops at the first key that no longer begins with the prefix.)
+ * Levels, base, the sequence number seq = n_0 + .. + n_(l-1) + j and the query
+ * list mean exactly what they mean in zscrc_device_find: `levels` is a HOST
+ * array of k <= ZSCRC_FIND_LEVELS_MAX lists over the one d_src, staged through
+ * the pinned staging, level 0 has priority, each level's keys ascend strictly
+ * in memcmp_raw order.  Query i is the prefix d_qsrc[key_off, +key_len) of
+ * d_queries[i]; the value words are never read.  A prefix of length 0 matches
+ * every key (a foreach with no prefix).  A prefix that does not lie inside [0,
+ * qsrc_size) is a bad query: its row range is empty and it is counted.
+ * A match: a key matches when it is at least as long as the prefix and its
+ * first key_len bytes are the prefix.  This is stricter than the reference,
+ * whose memcmp_raw(key, prefixlen, prefix, prefixlen) reads prefixlen bytes of
+ * a key that is shorter than the prefix; here a key that is a strict prefix of
+ * the prefix is no match and sorts before the range.  In a strictly ascending
+ * level the matches are a contiguous range from the lower bound of the prefix
+ * to the lower bound under a comparison that cuts every key to the prefix's
+ * length.
+ * Rows: over all levels, the matching keys of query i in ascending key order,
+ * each key once, taken from the first level that holds it.  A key whose
+ * winning record is a delete is dropped; with ZSCRC_SCAN_KEEP_DELETES it is
+ * kept as a row.  A row is the winning record's four words rebased, as
+ * zscrc_device_merge writes them (val_len of a delete as it came): the rows
+ * are a gather list for zscrc_device_gather, an input of zscrc_device_pack and
+ * a level of zscrc_device_find as they stand.
+ * Outputs: d_out (cap entries) holds the rows of query 0, then of query 1, and
+ * so on; d_offs (nq + 1 words): the rows of query i are d_out[d_offs[i],
+ * d_offs[i + 1]), d_offs[nq] the total; d_seq (NULL, or a word per row): the
+ * winning record's seq, from which level and location follow.
+ * d_res (device, ZSCRC_SCAN_RES_WORDS words):
+ *   [0] 0; ZSCRC_ZS_OVERFLOW; (uint64_t)(int64_t)ZSCRC_EINVAL = a level record
+ *       outside the source or, with ZSCRC_SCAN_CHECK_ORDER, an order offence,
+ *       both decided as in zscrc_device_find: nothing of d_out, d_offs or
+ *       d_seq is written
+ *   [1] nq; on EINVAL the smallest offending seq, bounds offences before order
+ *       offences
+ *   [2] the rows
+ *   [3] the candidates C: the records inside some query's range in some level,
+ *       summed over queries and levels -- the true sum even above cand_cap
+ *   [4] candidates superseded by a newer level   [5] winning deletes
+ *   [6] bad queries
+ *   [7] on EINVAL 1 for an order offence; on OVERFLOW 1 when C > cand_cap
+ *       (nothing but d_res is written and [2], [4], [5], [8], [9] are 0), 0
+ *       when the rows exceed cap (d_offs is written in full and exactly the
+ *       rows i < cap with their d_seq entries -- which rows those are follows
+ *       from their position, never from the order in which waves arrive; cap 0
+ *       with d_out NULL is the sizing call)
+ *   [8] the sum of key_len over the rows   [9] the sum of val_len over the rows
+ *       that are not deletes: with [2] the inputs of zscrc_device_pack_bound
+ *   [10], [11] 0
+ * Without KEEP_DELETES [2] + [4] + [5] == [3]; with it [2] + [4] == [3] and
+ * [5] counts the deletes among the rows.  Counts are integer atomics and
+ * workgroup sums only: two runs are bit for bit equal.  The results do not
+ * depend on `splitters` (zscrc_find_opts' meaning).  Without CHECK_ORDER a
+ * level that does not ascend is scanned all the same, inside its bounds: the
+ * rows are then unspecified, but every store stays inside d_out[0, cap),
+ * d_offs, d_seq and the scratch.
+ * Launches in stream order (the lookup's check and splitter tables; one bounds
+ * launch per level that is not empty on a persistent grid, the level's table in
+ * LDS; the scan of the range lengths; one thread a candidate that bisects its
+ * key in the query's range of every other level and so finds its slot among
+ * the query's candidates sorted by (key, level); the winners among the slots
+ * counted, scanned and scattered; the offsets, one thread a query that counts
+ * at most 1,023 slots of one block; one lane that seals); every grid
+ * is sized on the host from n_total, k, nq and cand_cap, no workgroup waits
+ * for another, nothing is copied to the host.
+ * Limits: find's; cand_cap <= 2^31 - 1.
+ * scratch: 16-byte aligned device memory of zscrc_device_scan_scratch_bytes
+ * bytes, or NULL for the per-device library scratch.  With up16(x) = x rounded
+ * up to 16 and P = nq * k the size is
+ *   128 + up16(32 (k + 1)) + (splitters > 1 ? 32 splitters k : 0)
+ *   + up16(4 P) + up16(8 (P + 1)) + up16(8 (P / 1024 + 1))
+ *   + up16(4 cand_cap) + up16(8 (cand_cap / 1024 + 1)):
+ * 12 bytes a (query, level) pair and 4 bytes a candidate -- its slot holds an
+ * index or a marker.  A multiple of 16, monotone in each argument; 0 = a bad
+ * option or an argument above its limit.
+ * ZSCRC_EINVAL before any device call: on zscrc_device_find's conditions (d_res
+ * NULL; nq > 0 with d_queries NULL; k > 0 with levels NULL; k > 64; a level
+ * with n > 0 and d_recs NULL; d_src NULL with src_size > 0, and likewise
+ * d_qsrc; src_size or qsrc_size > 2^62; n_total or nq > 2^31 - 1; scratch not
+ * 16-byte aligned; a bad option), and: d_offs NULL; cap > 0 with d_out NULL;
+ * cand_cap above its limit; an unknown flag. */
+typedef struct zscrc_scan_opts { uint32_t splitters; } zscrc_scan_opts;   /* NULL / 0 = default, zscrc_find_opts' meaning */
+#define ZSCRC_SCAN_KEEP_DELETES 1u
+#define ZSCRC_SCAN_CHECK_ORDER  2u
+#define ZSCRC_SCAN_RES_WORDS    12
+size_t zscrc_device_scan_scratch_bytes(size_t nq, size_t k, size_t cand_cap, const zscrc_scan_opts *opts);
+int zscrc_device_scan(const void *d_src, uint64_t src_size,
+                      const zscrc_merge_list *levels, size_t k,
+                      const void *d_qsrc, uint64_t qsrc_size,
+                      const struct zscrc_zs_record *d_queries, size_t nq,
+                      struct zscrc_zs_record *d_out, size_t cap, uint64_t *d_offs, uint64_t *d_seq,
+                      uint64_t *d_res, void *scratch, size_t cand_cap,
+                      const zscrc_scan_opts *opts, unsigned flags, void *stream);
+/* The same scan for lists and prefixes in host memory, one thread, no device:
+ * the same words for the same bytes.  The ranges come from the same inline
+ * functions as the kernels'; the rows from a merge with one cursor a level, a
+ * second algorithm that checks the device's rank method.  There is no
+ * candidate limit.  The argument checks are zscrc_device_scan's without
+ * scratch, cand_cap and options. */
+int zscrc_zs_scan(const void *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k,
+                  const void *qsrc, uint64_t qsrc_size, const struct zscrc_zs_record *queries, size_t nq,
+                  struct zscrc_zs_record *out, size_t cap, uint64_t *offs, uint64_t *seq,
+                  uint64_t res[ZSCRC_SCAN_RES_WORDS], unsigned flags);
+
 /* `consistent` for one process / one GPU (zsdb_consistent,
  * src/zeroskip.c:1399-1407, and tool/cmd-consistent.c:23-49 are stubs in the
  * reference): every .zsdb / header / commit CRC of the DB directory,

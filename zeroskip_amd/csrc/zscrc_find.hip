@@ -8,6 +8,8 @@
  *
  * Launches, all in stream order, no workgroup waiting for another one:
  *
+ *   (the first two are declared in zscrc_find_levels.h: zscrc_scan.hip's calls
+ *   begin with them too)
  *   find_check_kernel     one thread per level record: its level by binary
  *                         search of the staged prefix counts, the record
  *                         rebased and checked against the source, with
@@ -34,9 +36,133 @@
 #include <cstring>
 
 #include "../../include/zscrc.h"
+#include "zscrc_find_levels.h"
 #include "zscrc_find_order.h"
 #include "zscrc_internal.h"
 #include "zscrc_wg.h"
+
+/* what zscrc_find_levels.h declares: shared with zscrc_scan.hip */
+namespace zsfind {
+
+__global__ __launch_bounds__(WG) void find_check_kernel(Levels a)
+{
+    const uint64_t seq = (uint64_t)blockIdx.x * WG + threadIdx.x;
+    if (seq == 0)
+        for (int i = SC_COUNTERS; i < SC_WORDS; ++i)
+            a.sc[i] = 0;
+    if (seq >= a.n)
+        return;
+    const LevelD l = a.levels[zspack::find_rec(Firsts{a.levels}, a.filled, seq)];
+    const uint64_t j = seq - l.first;
+    zscrc_zs_record r = l.recs[j];
+    if (!zsmerge::rebase(r, l.base, a.src_size)) {
+        atomicMin(a.sc + SC_BAD, (unsigned long long)seq);
+        return;
+    }
+    if (!a.check_order || j == 0)
+        return;
+    zscrc_zs_record prev = l.recs[j - 1];
+    /* a predecessor outside the source is its own, smaller, offence */
+    if (zsmerge::rebase(prev, l.base, a.src_size) && order_offence(a.src, prev, r))
+        atomicMin(a.sc + SC_ORDER, (unsigned long long)seq);
+}
+
+__global__ __launch_bounds__(WG) void find_table_kernel(Levels a)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * WG + threadIdx.x;
+    if (t >= (uint64_t)a.filled * a.S || is_bad(a))
+        return;
+    const uint32_t li = (uint32_t)(t / a.S), j = (uint32_t)(t % a.S);
+    const LevelD l = a.levels[li];
+    const zscrc_zs_record r = l.recs[splitter_pos(j, a.levels[li + 1].first - l.first, a.S)];
+    table_store(a.tabs + (uint64_t)li * 4 * a.S, a.S, j, a.src, r.key_off + l.base, r.key_len);
+}
+
+/* The first launches of a call: the descriptors of the levels that hold
+ * records to d_levels through the pinned staging, the two minima preset, the
+ * check, the tables. */
+int launch_levels(const Levels &a, LevelD *d_levels, zs::Scratch &sc, const zscrc_merge_list *levels, size_t k,
+                         hipStream_t s)
+{
+    if (a.n) {
+        const size_t bytes = ((size_t)a.filled + 1) * sizeof(LevelD);
+        int rc = zs::stage_begin(sc, bytes);
+        if (rc)
+            return rc;
+        LevelD *h = static_cast<LevelD *>(sc.pin);
+        uint64_t first = 0;
+        for (size_t l = 0; l < k; ++l) {
+            if (!levels[l].n)
+                continue;
+            *h++ = LevelD{levels[l].d_recs, first, levels[l].base, l};
+            first += levels[l].n;
+        }
+        *h = LevelD{nullptr, first, 0, k};
+        rc = zs::stage_copy(sc, d_levels, bytes, s);
+        if (rc)
+            return rc;
+    }
+    if (hipMemsetAsync(a.sc, 0xFF, 16, s) != hipSuccess)
+        return ZSCRC_EHIP;
+    hipLaunchKernelGGL(find_check_kernel, dim3(a.n ? (a.n + WG - 1) / WG : 1), dim3(WG), 0, s, a);
+    if (a.n && a.S > 1)
+        hipLaunchKernelGGL(find_table_kernel, dim3((uint32_t)(((uint64_t)a.filled * a.S + WG - 1) / WG)), dim3(WG), 0,
+                           s, a);
+    return ZSCRC_OK;
+}
+
+/* The argument checks of the levels, the sources and the queries that the
+ * device and the host entries of the lookup and of the scan share; *n_total
+ * and *filled on success. */
+bool levels_args_ok(const void *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k,
+                           const void *qsrc, uint64_t qsrc_size, const void *queries, size_t nq, uint64_t *n_total,
+                           uint32_t *filled)
+{
+    if ((nq && !queries) || (k && !levels) || k > ZSCRC_FIND_LEVELS_MAX || (!src && src_size) ||
+        (!qsrc && qsrc_size) || src_size > zspack::SRC_MAX || qsrc_size > zspack::SRC_MAX || nq > N_MAX)
+        return false;
+    uint64_t n = 0;
+    *filled = 0;
+    for (size_t l = 0; l < k; ++l) {
+        if ((levels[l].n && !levels[l].d_recs) || levels[l].n > N_MAX - n)
+            return false;
+        n += levels[l].n;
+        *filled += levels[l].n != 0;
+    }
+    *n_total = n;
+    return true;
+}
+
+/* The check of the host forms, every record of every level in seq order: the
+ * smallest offending seq of each kind (U64_MAX: none) into res[0], [1], [7]
+ * as the seal kernels write them; false = an offence. */
+bool host_check(const uint8_t *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k,
+                       bool check_order, uint64_t *res)
+{
+    uint64_t bad = U64_MAX, order = U64_MAX, seq = 0;
+    for (size_t l = 0; l < k; ++l)
+        for (uint64_t j = 0; j < levels[l].n; ++j, ++seq) {
+            zscrc_zs_record r = levels[l].d_recs[j];
+            if (!zsmerge::rebase(r, levels[l].base, src_size)) {
+                if (bad == U64_MAX)
+                    bad = seq;
+                continue;
+            }
+            if (!check_order || j == 0 || order != U64_MAX)
+                continue;
+            zscrc_zs_record prev = levels[l].d_recs[j - 1];
+            if (zsmerge::rebase(prev, levels[l].base, src_size) && order_offence(src, prev, r))
+                order = seq;
+        }
+    if (bad == U64_MAX && order == U64_MAX)
+        return true;
+    res[0] = (uint64_t)(int64_t)ZSCRC_EINVAL;
+    res[1] = bad != U64_MAX ? bad : order;
+    res[7] = bad == U64_MAX;
+    return false;
+}
+
+} /* namespace zsfind */
 
 namespace {
 
@@ -45,49 +171,18 @@ using namespace zsdev;
 using zsmerge::rebase;
 using zspack::U64_MAX;
 
-/* the default: measured, DESIGN.md 2.6 (faster than no table on random, sorted
- * and whole-list batches; 2,048 is faster still on random keys only) */
-constexpr uint32_t DEF_SPLITTERS = 1024;
-/* the search's persistent grid: at most this many workgroups of WG threads
- * (zsfile.FIND_GRID_THREADS mirrors the product) */
-constexpr uint32_t GRID_MAX = 1024;
-/* ... and no more than are resident at once with their tables: an MI355X has
- * 256 CUs of 160 KiB LDS, each holding 8 workgroups of WG threads */
-constexpr uint32_t CUS = 256, LDS_PER_CU = 160 * 1024, WG_PER_CU = 8;
+/* scratch words after the check's two minima: the counters of res[2] .. res[6] */
+enum { SC_VALUES = SC_COUNTERS, SC_DELETES, SC_NONE, SC_BADQ, SC_SUMV };
 
-/* A level on the device: its records, the seq of its first one, its base,
- * its index among the caller's levels.  The entry one past the last level
- * that is not empty holds n_total. */
-struct LevelD {
-    const zscrc_zs_record *recs;
-    uint64_t first;
-    uint64_t base;
-    uint64_t level;
-};
-struct Firsts {
-    const LevelD *d;
-    __host__ __device__ uint64_t operator[](uint64_t i) const { return d[i].first; }
-};
-
-/* scratch words: the two minima, then the counters of res[2] .. res[6] */
-enum { SC_BAD = 0, SC_ORDER = 1, SC_VALUES = 2, SC_DELETES = 3, SC_NONE = 4, SC_BADQ = 5, SC_SUMV = 6, SC_WORDS = 16 };
-
-struct Find {
-    const uint8_t *src;
-    uint64_t src_size;
+/* A call: the levels with their check and tables (zscrc_find_levels.h), the
+ * queries and the outputs. */
+struct Find : Levels {
     const uint8_t *qsrc;
     uint64_t qsrc_size;
     const zscrc_zs_record *queries;
     Hit *hits;
     uint64_t *res;
-    unsigned long long *sc; /* SC_WORDS words */
-    const LevelD *levels;
-    uint64_t *tabs;         /* filled levels x 4 S words */
-    uint32_t filled;        /* levels that are not empty */
-    uint32_t n;             /* n_total */
     uint32_t nq;
-    uint32_t S;
-    uint32_t check_order;
 };
 
 /* One search launch: the level (n = 0: none holds a record), its index among
@@ -100,42 +195,6 @@ struct Pass {
     uint32_t first, last, last_level;
 };
 
-__device__ inline bool is_bad(const Find &a) { return (a.sc[SC_BAD] & a.sc[SC_ORDER]) != U64_MAX; }
-
-__global__ __launch_bounds__(WG) void find_check_kernel(Find a)
-{
-    const uint64_t seq = (uint64_t)blockIdx.x * WG + threadIdx.x;
-    if (seq == 0)
-        for (int i = SC_VALUES; i < SC_WORDS; ++i)
-            a.sc[i] = 0;
-    if (seq >= a.n)
-        return;
-    const LevelD l = a.levels[zspack::find_rec(Firsts{a.levels}, a.filled, seq)];
-    const uint64_t j = seq - l.first;
-    zscrc_zs_record r = l.recs[j];
-    if (!rebase(r, l.base, a.src_size)) {
-        atomicMin(a.sc + SC_BAD, (unsigned long long)seq);
-        return;
-    }
-    if (!a.check_order || j == 0)
-        return;
-    zscrc_zs_record prev = l.recs[j - 1];
-    /* a predecessor outside the source is its own, smaller, offence */
-    if (rebase(prev, l.base, a.src_size) && order_offence(a.src, prev, r))
-        atomicMin(a.sc + SC_ORDER, (unsigned long long)seq);
-}
-
-__global__ __launch_bounds__(WG) void find_table_kernel(Find a)
-{
-    const uint64_t t = (uint64_t)blockIdx.x * WG + threadIdx.x;
-    if (t >= (uint64_t)a.filled * a.S || is_bad(a))
-        return;
-    const uint32_t li = (uint32_t)(t / a.S), j = (uint32_t)(t % a.S);
-    const LevelD l = a.levels[li];
-    const zscrc_zs_record r = l.recs[splitter_pos(j, a.levels[li + 1].first - l.first, a.S)];
-    table_store(a.tabs + (uint64_t)li * 4 * a.S, a.S, j, a.src, r.key_off + l.base, r.key_len);
-}
-
 __global__ __launch_bounds__(WG) void find_search_kernel(Find a, Pass p)
 {
     extern __shared__ __align__(16) uint8_t lds[];
@@ -143,13 +202,7 @@ __global__ __launch_bounds__(WG) void find_search_kernel(Find a, Pass p)
         return;
     uint64_t *s_tab = reinterpret_cast<uint64_t *>(lds);
     const uint32_t S = p.lv.n ? a.S : 1;
-    if (S > 1) {
-        const ulonglong2 *g = reinterpret_cast<const ulonglong2 *>(p.tab);
-        ulonglong2 *s = reinterpret_cast<ulonglong2 *>(lds);
-        for (uint32_t i = threadIdx.x; i < 2 * S; i += WG)
-            s[i] = g[i];
-        __syncthreads();
-    }
+    table_to_lds(lds, p.tab, S);
     uint64_t values = 0, deletes = 0, none = 0, badq = 0, sumv = 0;
     const uint64_t stride = (uint64_t)gridDim.x * WG;
     for (uint64_t i = (uint64_t)blockIdx.x * WG + threadIdx.x; i < a.nq; i += stride) {
@@ -230,12 +283,7 @@ __global__ void find_seal_kernel(Find a)
     a.res[6] = a.sc[SC_SUMV];
 }
 
-/* The splitters of a call; 0 = a bad option. */
-uint32_t splitters_of(const zscrc_find_opts *o)
-{
-    const uint32_t s = o && o->splitters ? o->splitters : DEF_SPLITTERS;
-    return pow2(s) && s <= S_MAX ? s : 0;
-}
+uint32_t splitters_of(const zscrc_find_opts *o) { return zsfind::splitters_of(o ? o->splitters : 0); }
 
 /* The pieces of the scratch for k levels: the words, the descriptors of the
  * levels and the entry that ends them, a table for every level. */
@@ -259,36 +307,11 @@ int launch(Find &a, const Plan &p, void *scratch, zs::Scratch &sc, const zscrc_m
     LevelD *d_levels = reinterpret_cast<LevelD *>(base + p.levels_at);
     a.levels = d_levels;
     a.tabs = reinterpret_cast<uint64_t *>(base + p.tabs_at);
-    if (a.n) {
-        /* the descriptors of the levels that hold records, through the pinned staging */
-        const size_t bytes = ((size_t)a.filled + 1) * sizeof(LevelD);
-        int rc = zs::stage_begin(sc, bytes);
-        if (rc)
-            return rc;
-        LevelD *h = static_cast<LevelD *>(sc.pin);
-        uint64_t first = 0;
-        for (size_t l = 0; l < k; ++l) {
-            if (!levels[l].n)
-                continue;
-            *h++ = LevelD{levels[l].d_recs, first, levels[l].base, l};
-            first += levels[l].n;
-        }
-        *h = LevelD{nullptr, first, 0, k};
-        rc = zs::stage_copy(sc, d_levels, bytes, s);
-        if (rc)
-            return rc;
-    }
-    if (hipMemsetAsync(a.sc, 0xFF, 16, s) != hipSuccess)
-        return ZSCRC_EHIP;
-    hipLaunchKernelGGL(find_check_kernel, dim3(a.n ? (a.n + WG - 1) / WG : 1), dim3(WG), 0, s, a);
-    if (a.n && a.S > 1)
-        hipLaunchKernelGGL(find_table_kernel, dim3((uint32_t)(((uint64_t)a.filled * a.S + WG - 1) / WG)), dim3(WG), 0,
-                           s, a);
+    const int rc = launch_levels(a, d_levels, sc, levels, k, s);
+    if (rc)
+        return rc;
     if (a.nq) {
-        const uint32_t lds = a.S > 1 ? a.S * 32 : 64;
-        const uint32_t per_cu = LDS_PER_CU / lds < WG_PER_CU ? LDS_PER_CU / lds : WG_PER_CU;
-        const uint32_t resident = CUS * per_cu < GRID_MAX ? CUS * per_cu : GRID_MAX;
-        const uint32_t blocks = (a.nq + WG - 1) / WG, grid = blocks < resident ? blocks : resident;
+        const uint32_t lds = table_lds(a.S), grid = table_grid(a.S, a.nq);
         Pass ps{};
         ps.first = 1;
         uint32_t li = 0;
@@ -318,20 +341,8 @@ bool args_ok(const void *src, uint64_t src_size, const zscrc_merge_list *levels,
              uint64_t qsrc_size, const void *queries, size_t nq, const void *hits, const void *res, unsigned flags,
              uint64_t *n_total, uint32_t *filled)
 {
-    if (!res || (nq && (!queries || !hits)) || (k && !levels) || k > ZSCRC_FIND_LEVELS_MAX || (!src && src_size) ||
-        (!qsrc && qsrc_size) || src_size > zspack::SRC_MAX || qsrc_size > zspack::SRC_MAX || nq > N_MAX ||
-        (flags & ~ZSCRC_FIND_CHECK_ORDER))
-        return false;
-    uint64_t n = 0;
-    *filled = 0;
-    for (size_t l = 0; l < k; ++l) {
-        if ((levels[l].n && !levels[l].d_recs) || levels[l].n > N_MAX - n)
-            return false;
-        n += levels[l].n;
-        *filled += levels[l].n != 0;
-    }
-    *n_total = n;
-    return true;
+    return res && !(nq && !hits) && !(flags & ~ZSCRC_FIND_CHECK_ORDER) &&
+           levels_args_ok(src, src_size, levels, k, qsrc, qsrc_size, queries, nq, n_total, filled);
 }
 
 } /* namespace */
@@ -385,28 +396,8 @@ int zscrc_zs_find(const void *src, uint64_t src_size, const zscrc_merge_list *le
         return ZSCRC_EINVAL;
     const uint8_t *s = static_cast<const uint8_t *>(src), *qs = static_cast<const uint8_t *>(qsrc);
     memset(res, 0, ZSCRC_FIND_RES_WORDS * 8);
-    /* the check: every record of every level */
-    uint64_t bad = U64_MAX, order = U64_MAX, seq = 0;
-    for (size_t l = 0; l < k; ++l)
-        for (uint64_t j = 0; j < levels[l].n; ++j, ++seq) {
-            zscrc_zs_record r = levels[l].d_recs[j];
-            if (!rebase(r, levels[l].base, src_size)) {
-                if (bad == U64_MAX)
-                    bad = seq;
-                continue;
-            }
-            if (!(flags & ZSCRC_FIND_CHECK_ORDER) || j == 0 || order != U64_MAX)
-                continue;
-            zscrc_zs_record prev = levels[l].d_recs[j - 1];
-            if (rebase(prev, levels[l].base, src_size) && order_offence(s, prev, r))
-                order = seq;
-        }
-    if (bad != U64_MAX || order != U64_MAX) {
-        res[0] = (uint64_t)(int64_t)ZSCRC_EINVAL;
-        res[1] = bad != U64_MAX ? bad : order;
-        res[7] = bad == U64_MAX;
+    if (!host_check(s, src_size, levels, k, flags & ZSCRC_FIND_CHECK_ORDER, res))
         return ZSCRC_OK;
-    }
     res[1] = nq;
     for (size_t i = 0; i < nq; ++i) {
         Hit h{NONE, 0, 0, 0};

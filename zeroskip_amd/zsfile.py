@@ -509,6 +509,160 @@ def device_get(d_src: torch.Tensor, levels, d_qsrc: torch.Tensor, queries: torch
     return values, offs, crc, hits, fres, gres
 
 
+class ScanOpts(ctypes.Structure):
+    """zscrc_scan_opts (include/zscrc.h); 0 = the default."""
+    _fields_ = [("splitters", ctypes.c_uint32)]
+
+
+SCAN_RES_WORDS = 12  # ZSCRC_SCAN_RES_WORDS
+SCAN_KEEP_DELETES = 1  # ZSCRC_SCAN_KEEP_DELETES
+SCAN_CHECK_ORDER = 2  # ZSCRC_SCAN_CHECK_ORDER
+SCAN_GRID_THREADS = 1024 * 256  # zscrc_scan.hip GRID_MAX * WG: the rank's persistent grid at its largest
+SCAN_BLOCK = 1024  # zscrc_scan.hip BLOCK_RECS: the pairs and the slots one workgroup sums and scans
+
+
+def _scan_flags(keep_deletes: bool, check_order: bool) -> int:
+    return (SCAN_KEEP_DELETES if keep_deletes else 0) | (SCAN_CHECK_ORDER if check_order else 0)
+
+
+def device_scan_scratch_bytes(nq: int, k: int, cand_cap: int, splitters: int = 0) -> int:
+    """zscrc_device_scan_scratch_bytes; 0 = a bad option or an argument above its limit."""
+    return lib().zscrc_device_scan_scratch_bytes(nq, k, cand_cap, ctypes.byref(ScanOpts(splitters)))
+
+
+def device_scan(d_src: torch.Tensor, levels, d_qsrc: torch.Tensor, queries: torch.Tensor, keep_deletes: bool = False,
+                check_order: bool = False, cap: int | None = None, cand_cap: int | None = None, splitters: int = 0,
+                out: tuple | None = None, scratch: torch.Tensor | None = None):
+    """A batch of key prefixes scanned in device-resident sorted record lists
+    on the GPU (zscrc_device_scan): (rows, offs, seq, res) int64 device
+    tensors.  d_src, levels, d_qsrc and queries are device_find's; query i is
+    a prefix, and an empty one matches every key.  rows [cap, 4]: for every
+    query in turn the records whose key begins with its prefix, in key order,
+    each key once from the first level that holds it, rebased as
+    repack.device_merge writes them; a key whose winning record is a delete
+    is left out unless keep_deletes.  The rows of query i are
+    rows[offs[i]:offs[i + 1]], offs[nq] the total; seq [cap]: the winning
+    record's sequence number.  res: [code (0; 3 = more rows than cap, or,
+    with res[7] = 1, more candidates than cand_cap: nothing written; -1 = a
+    level record outside d_src or, with check_order, a key not above its
+    predecessor's: nothing written), nq or the first offending sequence
+    number, rows, candidates, superseded, winning deletes, bad queries, the
+    overflow's or offence's kind, sum of the rows' key lengths, sum of their
+    value lengths, 0, 0].  With cap and cand_cap (the candidates the scratch
+    has room for) the call is asynchronous on the current stream.  Otherwise
+    it reads res and sizes itself: cand_cap starts at the levels' record
+    count and the call is made again once with the reported res[3] on a
+    candidate overflow; cap=None makes the sizing call first and allocates
+    res[2] rows.  splitters: device_find's; the result never depends on it.
+    out: preallocated (rows, offs, seq | None, res); scratch: a 16-byte
+    aligned uint8 tensor of device_scan_scratch_bytes(nq, k, cand_cap) bytes
+    (default: the library's own, stream-ordered)."""
+    dev = d_src.device
+    arr, k = _find_levels(levels, lambda r: r.data_ptr())
+    for recs, _ in levels:
+        assert recs.dtype == torch.int64 and recs.is_contiguous()
+    nq = int(queries.shape[0])
+    assert queries.dtype == torch.int64 and queries.is_contiguous() and (nq == 0 or queries.shape[1] == 4)
+    src_bytes = d_src.numel() * d_src.element_size()
+    q_bytes = d_qsrc.numel() * d_qsrc.element_size()
+    opts = ScanOpts(splitters)
+    flags = _scan_flags(keep_deletes, check_order)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    sp = None if scratch is None else scratch.data_ptr()
+
+    def call(rows, rcap, offs, seq, res, ccap):
+        with torch.cuda.device(dev):
+            check(lib().zscrc_device_scan(
+                d_src.data_ptr() if src_bytes else None, src_bytes, arr, k, d_qsrc.data_ptr() if q_bytes else None,
+                q_bytes, queries.data_ptr() if nq else None, nq,
+                rows.data_ptr() if rows is not None and rcap else None, rcap, offs.data_ptr(),
+                None if seq is None or not rcap else seq.data_ptr(), res.data_ptr(), sp, ccap, ctypes.byref(opts),
+                flags, stream), "zscrc_device_scan")
+
+    if out is not None:
+        rows, offs, seq, res = out
+        assert offs.numel() >= nq + 1 and res.numel() >= SCAN_RES_WORDS and cand_cap is not None
+        cap = int(rows.shape[0]) if cap is None else cap
+        assert rows.numel() >= 4 * cap and (seq is None or seq.numel() >= cap)
+        call(rows, cap, offs, seq, res, cand_cap)
+        return rows, offs, seq, res
+    offs = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+    res = torch.empty(SCAN_RES_WORDS, dtype=torch.int64, device=dev)
+
+    def alloc(n):
+        return torch.empty((n, 4), dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int64, device=dev)
+
+    if cap is not None and cand_cap is not None:
+        rows, seq = alloc(cap)
+        call(rows, cap, offs, seq, res, cand_cap)
+        return rows, offs, seq, res
+    sized = cand_cap is not None
+    if not sized:
+        cand_cap = sum(int(r.shape[0]) for r, _ in levels)
+    rows, seq = alloc(cap or 0)
+    call(rows, cap or 0, offs, seq, res, cand_cap)
+    code, nrows, cands, kind = (int(v) for v in res[[0, 2, 3, 7]].cpu())
+    if code == 3 and kind == 1 and not sized:
+        cand_cap = cands
+        call(rows, cap or 0, offs, seq, res, cand_cap)
+        code, nrows, cands, kind = (int(v) for v in res[[0, 2, 3, 7]].cpu())
+    if cap is None and code == 3 and kind == 0:
+        rows, seq = alloc(nrows)
+        call(rows, nrows, offs, seq, res, cand_cap)
+    return rows, offs, seq, res
+
+
+def scan(src, levels, qsrc, queries, keep_deletes: bool = False, check_order: bool = False, cap: int | None = None):
+    """device_scan for lists and prefixes in host memory (zscrc_zs_scan, one
+    thread, no device): (rows int64 [cap, 4], offs int64 [nq + 1], seq int64
+    [cap], res int64 [12]) numpy arrays, the same words for the same bytes.
+    src, qsrc: bytes or uint8 arrays; levels: (recs, base) with recs [n, 4]
+    uint64 or int64 arrays; queries [nq, 4].  cap: the rows the buffer holds
+    (default: a sizing call first)."""
+    s, sp, sn = _host(src)
+    q, qp, qn = _host(qsrc)
+    levels = [(np.ascontiguousarray(r).view(np.int64).reshape(-1, 4), b) for r, b in levels]
+    arr, k = _find_levels(levels, lambda r: r.ctypes.data)
+    qr = np.ascontiguousarray(queries).view(np.int64).reshape(-1, 4)
+    nq = len(qr)
+    offs = np.empty(nq + 1, np.int64)
+    res = np.empty(SCAN_RES_WORDS, np.int64)
+    flags = _scan_flags(keep_deletes, check_order)
+
+    def call(rows, seq, rcap):
+        check(lib().zscrc_zs_scan(sp if sn else None, sn, arr, k, qp if qn else None, qn,
+                                  qr.ctypes.data if nq else None, nq, rows.ctypes.data if rcap else None, rcap,
+                                  offs.ctypes.data, seq.ctypes.data if rcap else None, res.ctypes.data, flags),
+              "zscrc_zs_scan")
+
+    if cap is None:
+        call(None, None, 0)
+        cap = int(res[2]) if int(res[0]) != -1 else 0
+    rows, seq = np.empty((cap, 4), np.int64), np.empty(cap, np.int64)
+    call(rows, seq, cap)
+    return rows, offs, seq, res
+
+
+def device_foreach(d_src: torch.Tensor, levels, d_qsrc: torch.Tensor, queries: torch.Tensor,
+                   keep_deletes: bool = False, crcs: bool = False, check_order: bool = False, splitters: int = 0,
+                   tile_bytes: int = 0):
+    """An ordered iteration on the GPU: device_scan, then device_gather over
+    its rows, in one call: (rows, offs, values, value_offs, crcs | None,
+    scan_res, gather_res).  Row j of query i, rows[offs[i] + j], has the key
+    d_src[key_off:key_off + key_len] and the value values[value_offs[r]:
+    value_offs[r + 1]], r its row index -- it is to device_scan what
+    device_get is to device_find.  Both stages size themselves from their
+    result words.  A scan that refuses its levels (scan_res[0] = -1) writes
+    no row; the gather is then not run and values, value_offs, crcs and
+    gather_res are None."""
+    rows, offs, _, sres = device_scan(d_src, levels, d_qsrc, queries, keep_deletes=keep_deletes,
+                                      check_order=check_order, splitters=splitters)
+    if int(sres[0].cpu()) != 0:
+        return rows, offs, None, None, None, sres, None
+    values, voffs, crc, gres = device_gather(d_src, rows, crcs=crcs, tile_bytes=tile_bytes)
+    return rows, offs, values, voffs, crc, sres, gres
+
+
 def verify_device_images(d_arena: torch.Tensor, images) -> list:
     """verify_device_image() for the k active or finalised images [(off,
     size)] of a device-resident arena in one call (zscrc_device_verify_images):
