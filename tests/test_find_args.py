@@ -80,9 +80,8 @@ def test_scratch_bytes():
             need = zsfile.device_find_scratch_bytes(k, s)
             each = s or zsfile.FIND_DEFAULT_SPLITTERS
             table = 32 * each * k if each > 1 else 0
-            # a few words, 32 bytes a level and the entry that ends them, a table a level
-            assert need % 16 == 0 and need > last and table + 32 * (k + 1) <= need <= table + 32 * (k + 1) + 256, \
-                (k, s, need)
+            # 16 words, 32 bytes a level and the entry that ends them, a table a level
+            assert need > last and need == 128 + (32 * (k + 1) + 15) // 16 * 16 + table, (k, s, need)
             last = need
     for s in (3, 48, 4096):
         for k in (0, 1, 64):

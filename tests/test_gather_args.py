@@ -64,9 +64,9 @@ def test_scratch_bytes():
         for nq in (0, 1, 2, 1023, 1024, 1025, 4096, 4097, 1 << 20, (1 << 20) + 1, N_MAX):
             need = zsfile.device_gather_scratch_bytes(nq, t)
             blocks = (nq + 1023) // 1024
-            # a few words, a sum a block of 1,024 items, and for the CRC batch an offset and a length an item
-            assert need % 16 == 0 and need > last and 16 * nq + 8 * blocks <= need <= 16 * nq + 8 * blocks + 256, \
-                (nq, t, need)
+            # 16 words, a sum a block of 1,024 items and one more, and for the CRC batch an offset and a length
+            # an item, one 8-byte array behind the other, the whole rounded up to 16
+            assert need > last and need == (8 * (16 + blocks + 1 + 2 * nq) + 15) // 16 * 16, (nq, t, need)
             last = need
     for t in (1, 32, 48, 3000, 1 << 17):
         for nq in (0, 1, 4096):

@@ -87,6 +87,27 @@ def test_empty_and_one_record(gpu, cases):
     _same(mixed, gpu, tile=64)
 
 
+def test_filled_lists_between_empty_ones_with_three_bases(gpu):
+    """(empty, 3 records, empty, 1 record, empty): the index of a list among those that are not empty differs from
+    the caller's at both ends and in the middle, and each staged descriptor must carry its own list's base."""
+    img = mc.from_items("img", [(b"b", b"old"), (b"a", None), (b"c", b"3"), (b"b", b"new")])
+    recs, size = img.lists[0][0], 128
+    assert len(img.src) <= size
+    copy = img.src + b"\xEE" * (size - len(img.src))
+    none = np.zeros((0, 4), np.uint64)
+    c = mc.Case("empty_3_empty_1_empty", b"\xEE" * size + copy + copy,
+                [(none, 0), (recs[:3], size), (none, 2 * size), (recs[3:], 2 * size), (none, size)])
+    assert len(c.src) == 384 and c.n == 4
+    for drop in (False, True):
+        r = _same(c, gpu, drop)
+        _same(c, gpu, drop, tile=64)
+        # a (a delete), b (the later list's, superseding one), c
+        assert [int(r[i]) for i in (1, 2, 6, 7)] == ([2, 4, 1, 1] if drop else [3, 4, 1, 0])
+    want = c.model(False)[0]
+    assert c.pairs(want) == [(b"a", None), (b"b", b"new"), (b"c", b"3")]
+    assert int(want[1, 0]) >= 2 * size > int(want[2, 0]) >= size
+
+
 # ------------------------------------------------------------------ tile counts
 @pytest.mark.parametrize("tile", TILES, ids=TILE_IDS)
 def test_record_counts_around_the_tile(gpu, cases, tile):

@@ -51,16 +51,21 @@ def test_too_many_records_or_lists_are_einval():
     assert lib().zscrc_device_merge(PTR, 4096, many, WALK_MULTI_MAX + 1, OUT, 4, PTR, None, None, 0, None) == EINVAL
 
 
+def _up16(v):
+    return (v + 15) // 16 * 16
+
+
 def test_scratch_bytes():
     for tile in (0, 64, 256, 1024, 2048):
         last = 0
         for n in list(range(0, 40)) + [63, 64, 65, 1023, 1024, 1025, 2049, 1 << 20, (1 << 20) + 1, (1 << 21) + 3,
                                        (1 << 31) - 1]:
             need = repack.device_merge_scratch_bytes(n, tile)
-            # 32 + 2 x 16 + 1 bytes a record, 24 a list that is not empty, block counts and a few words
-            lists = min(n, WALK_MULTI_MAX)
-            assert need % 16 == 0 and need >= last and 65 * n < need <= 65 * n + 24 * lists + n // 256 + 256, \
-                (n, tile, need)
+            # 16 words, 24 bytes a list that is not empty and the entry that ends them, 32 + 2 x 16 bytes a record,
+            # a count a block of 1,024 records and one more, a flag a record: every piece rounded up to 16
+            lists, blocks = min(n, WALK_MULTI_MAX), (n + 1023) // 1024
+            assert need >= last and need == 128 + _up16(24 * (lists + 1)) + 64 * n + _up16(4 * (blocks + 1)) + \
+                _up16(n), (n, tile, need)
             last = need
     for tile in (32, 48, 4096):
         for n in (0, 1, 5000):

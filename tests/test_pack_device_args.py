@@ -81,8 +81,10 @@ def test_scratch_bytes():
         last = 0
         for n in list(range(0, 40)) + [1023, 1024, 1025, 2047, 2048, 2049, 1 << 20, (1 << 21) + 3, (1 << 31) - 1]:
             need = repack.device_pack_scratch_bytes(n, tile)
-            # 8 bytes a record, block sums and a few words
-            assert need % 16 == 0 and need >= last and 8 * n < need <= 8 * n + n // 64 + 512, (n, tile, need)
+            # 16 words, a sum a block of 1,024 records and one more, a start a record and one more, one 8-byte
+            # array behind the other, the whole rounded up to 16
+            blocks = (n + 1023) // 1024
+            assert need >= last and need == (8 * (16 + blocks + 1 + n + 1) + 15) // 16 * 16, (n, tile, need)
             last = need
     for tile in (48, 32, 1 << 17):
         for n in (0, 1, 5000):

@@ -34,9 +34,10 @@
  * on the device.  A result code other than 0 makes every later kernel return
  * at once, and the span descriptors empty.
  *
- * The sums and prefix sums are zscrc_wg.h's with an addition that saturates
+ * The sums and prefix sums are zscrc_wg.h's with its addition that saturates
  * (pack_scan_kernel: scan_counts); the scratch of a call comes through
- * zs::with_scratch (zscrc_internal.h, zscrc_scratch.cpp).
+ * zs::with_scratch (zscrc_internal.h, zscrc_scratch.cpp), laid out by carve();
+ * the option rule, the pointer checks and the copy's grid: zsdev's, there too.
  */
 #include <hip/hip_runtime.h>
 
@@ -79,11 +80,6 @@ struct Pack {
     uint64_t *start;  /* n + 1 */
     uint64_t nblocks;
     uint64_t tile;
-};
-
-/* Sums of lengths saturate (zscrc_pack_layout.h): the addition of the scans. */
-struct SatAdd {
-    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return sat_add(a, b); }
 };
 
 /* The serialised length of record i, 0 past the list or for a bad record. */
@@ -184,8 +180,6 @@ __device__ inline uint64_t record_word(const Pack &a, const zscrc_zs_record &r, 
     return pc.n ? gather8(a.src + pc.src_off, pc.n) : pc.word;
 }
 
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
 __global__ __launch_bounds__(WG) void pack_copy_kernel(Pack a)
 {
     __shared__ uint64_t s_start[LDS_STARTS];
@@ -282,24 +276,21 @@ __global__ __launch_bounds__(64) void pack_seal_kernel(Pack a, Header h)
 }
 
 /* The tile of a call; 0 = a bad option. */
-uint64_t tile_of(const zscrc_pack_opts *o)
-{
-    const uint64_t t = o && o->tile_bytes ? o->tile_bytes : DEF_TILE;
-    return pow2(t) && t >= TILE_MIN && t <= TILE_MAX ? t : 0;
-}
+uint64_t tile_of(const zscrc_pack_opts *o) { return pow2_opt(o ? o->tile_bytes : 0, DEF_TILE, TILE_MIN, TILE_MAX); }
 
-uint64_t blocks_of(uint64_t n) { return (n + BLOCK_RECS - 1) / BLOCK_RECS; }
-
-size_t scratch_need(uint64_t n)
+/* The pieces of the scratch into a, one 8-byte array behind the other; the bytes. */
+size_t carve(Pack &a, zs::Carve c)
 {
-    return up16((size_t)((SC_WORDS + blocks_of(n) + 1 + n + 1) * 8));
+    a.nblocks = blocks_of(a.n);
+    a.sc = c.take<uint64_t>(SC_WORDS, 16);
+    a.bsum = c.take<uint64_t>(a.nblocks + 1);
+    a.start = c.take<uint64_t>(a.n + 1);
+    return up16(c.bytes());
 }
 
 int launch(Pack &a, void *scratch, const Header &h, hipStream_t s)
 {
-    a.sc = static_cast<uint64_t *>(scratch);
-    a.bsum = a.sc + SC_WORDS;
-    a.start = a.bsum + a.nblocks + 1;
+    carve(a, zs::Carve(scratch));
     if (a.n) {
         if (hipMemsetAsync(a.sc + SC_BAD, 0xFF, 8, s) != hipSuccess)
             return ZSCRC_EHIP;
@@ -312,18 +303,12 @@ int launch(Pack &a, void *scratch, const Header &h, hipStream_t s)
     if (a.out_cap < 64)
         return ZSCRC_OK;
     if (a.n) {
-        int dev = 0, ncu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
+        /* the region's size is on the device only */
+        unsigned g;
+        if (copy_grid(a.out_cap, a.tile, COPY_WG_PER_CU, &g) != ZSCRC_OK)
             return ZSCRC_EHIP;
         hipLaunchKernelGGL(pack_prefix_kernel, dim3((unsigned)a.nblocks), dim3(WG), 0, s, a);
-        /* the region's size is on the device only: a grid for the most the
-         * output can hold, capped; a workgroup takes a run of the tiles there are */
-        uint64_t g = (a.out_cap + a.tile - 1) / a.tile;
-        const uint64_t gmax = (uint64_t)ncu * COPY_WG_PER_CU;
-        if (g > gmax)
-            g = gmax;
-        hipLaunchKernelGGL(pack_copy_kernel, dim3((unsigned)g), dim3(WG), 0, s, a);
+        hipLaunchKernelGGL(pack_copy_kernel, dim3(g), dim3(WG), 0, s, a);
     }
     if (hipGetLastError() != hipSuccess)
         return ZSCRC_EHIP;
@@ -352,20 +337,18 @@ size_t zscrc_device_pack_scratch_bytes(size_t n, const zscrc_pack_opts *opts)
 {
     if (!tile_of(opts) || n > N_MAX)
         return 0;
-    return scratch_need(n);
+    Pack a{};
+    a.n = n;
+    return carve(a, zs::Carve(nullptr));
 }
 
 int zscrc_device_pack(const void *d_src, uint64_t src_size, const struct zscrc_zs_record *d_recs, size_t n,
                       const uint8_t uuid[16], uint32_t startidx, uint32_t endidx, void *d_out, uint64_t out_cap,
                       uint64_t *d_res, void *scratch, const zscrc_pack_opts *opts, unsigned flags, void *stream)
 {
-    const uintptr_t so = reinterpret_cast<uintptr_t>(d_src), oo = reinterpret_cast<uintptr_t>(d_out);
     const uint64_t tile = tile_of(opts);
-    if (!d_res || !uuid || (n && !d_recs) || (!d_src && src_size) || (out_cap && !d_out) || (oo & 15) ||
-        (reinterpret_cast<uintptr_t>(scratch) & 15) || flags || !tile || n > N_MAX || src_size > SRC_MAX ||
-        out_cap > UINTPTR_MAX - oo || src_size > UINTPTR_MAX - so)
-        return ZSCRC_EINVAL;
-    if (out_cap && src_size && oo < so + src_size && so < oo + out_cap)
+    if (!d_res || !uuid || (n && !d_recs) || (reinterpret_cast<uintptr_t>(scratch) & 15) || flags || !tile ||
+        n > N_MAX || src_size > SRC_MAX || !src_out_ok(d_src, src_size, d_out, out_cap, true))
         return ZSCRC_EINVAL;
     Pack a{};
     a.src = static_cast<const uint8_t *>(d_src);
@@ -375,11 +358,10 @@ int zscrc_device_pack(const void *d_src, uint64_t src_size, const struct zscrc_z
     a.out = static_cast<uint8_t *>(d_out);
     a.out_cap = out_cap;
     a.res = d_res;
-    a.nblocks = blocks_of(n);
     a.tile = tile;
     const Header h = header_words(uuid, startidx, endidx);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return zs::with_scratch(scratch, scratch_need(n), false, s,
+    return zs::with_scratch(scratch, carve(a, zs::Carve(nullptr)), false, s,
                             [&](void *p, zs::Scratch *) { return launch(a, p, h, s); });
 }
 

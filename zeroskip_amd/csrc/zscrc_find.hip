@@ -8,8 +8,8 @@
  *
  * Launches, all in stream order, no workgroup waiting for another one:
  *
- *   (the first two are declared in zscrc_find_levels.h: zscrc_scan.hip's calls
- *   begin with them too)
+ *   (the first two are launched by zscrc_find_levels.h's launch_levels:
+ *   zscrc_scan.hip's calls begin with them too)
  *   find_check_kernel     one thread per level record: its level by binary
  *                         search of the staged prefix counts, the record
  *                         rebased and checked against the source, with
@@ -29,6 +29,9 @@
  *
  * Every grid comes from n_total, k and nq on the host.  An offending record
  * makes every launch after the check return at once.
+ *
+ * The level descriptors and their staging are zscrc_lists.h's; the scratch of
+ * a call is laid out by carve() on top of zscrc_find_levels.h's carve_levels.
  */
 #include <hip/hip_runtime.h>
 
@@ -41,7 +44,8 @@
 #include "zscrc_internal.h"
 #include "zscrc_wg.h"
 
-/* what zscrc_find_levels.h declares: shared with zscrc_scan.hip */
+/* what zscrc_find_levels.h declares, and the two kernels launch_levels
+ * launches: shared with zscrc_scan.hip */
 namespace zsfind {
 
 __global__ __launch_bounds__(WG) void find_check_kernel(Levels a)
@@ -52,7 +56,7 @@ __global__ __launch_bounds__(WG) void find_check_kernel(Levels a)
             a.sc[i] = 0;
     if (seq >= a.n)
         return;
-    const LevelD l = a.levels[zspack::find_rec(Firsts{a.levels}, a.filled, seq)];
+    const ListD l = a.levels[zspack::find_rec(Firsts{a.levels}, a.filled, seq)];
     const uint64_t j = seq - l.first;
     zscrc_zs_record r = l.recs[j];
     if (!zsmerge::rebase(r, l.base, a.src_size)) {
@@ -73,32 +77,15 @@ __global__ __launch_bounds__(WG) void find_table_kernel(Levels a)
     if (t >= (uint64_t)a.filled * a.S || is_bad(a))
         return;
     const uint32_t li = (uint32_t)(t / a.S), j = (uint32_t)(t % a.S);
-    const LevelD l = a.levels[li];
+    const ListD l = a.levels[li];
     const zscrc_zs_record r = l.recs[splitter_pos(j, a.levels[li + 1].first - l.first, a.S)];
     table_store(a.tabs + (uint64_t)li * 4 * a.S, a.S, j, a.src, r.key_off + l.base, r.key_len);
 }
 
-/* The first launches of a call: the descriptors of the levels that hold
- * records to d_levels through the pinned staging, the two minima preset, the
- * check, the tables. */
-int launch_levels(const Levels &a, LevelD *d_levels, zs::Scratch &sc, const zscrc_merge_list *levels, size_t k,
-                         hipStream_t s)
+int launch_levels(const Levels &a, zs::Scratch &sc, const zscrc_merge_list *levels, size_t k, hipStream_t s)
 {
     if (a.n) {
-        const size_t bytes = ((size_t)a.filled + 1) * sizeof(LevelD);
-        int rc = zs::stage_begin(sc, bytes);
-        if (rc)
-            return rc;
-        LevelD *h = static_cast<LevelD *>(sc.pin);
-        uint64_t first = 0;
-        for (size_t l = 0; l < k; ++l) {
-            if (!levels[l].n)
-                continue;
-            *h++ = LevelD{levels[l].d_recs, first, levels[l].base, l};
-            first += levels[l].n;
-        }
-        *h = LevelD{nullptr, first, 0, k};
-        rc = zs::stage_copy(sc, d_levels, bytes, s);
+        const int rc = zsdev::stage_lists(sc, levels, k, a.filled, a.levels, s);
         if (rc)
             return rc;
     }
@@ -111,33 +98,16 @@ int launch_levels(const Levels &a, LevelD *d_levels, zs::Scratch &sc, const zscr
     return ZSCRC_OK;
 }
 
-/* The argument checks of the levels, the sources and the queries that the
- * device and the host entries of the lookup and of the scan share; *n_total
- * and *filled on success. */
-bool levels_args_ok(const void *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k,
-                           const void *qsrc, uint64_t qsrc_size, const void *queries, size_t nq, uint64_t *n_total,
-                           uint32_t *filled)
+bool levels_args_ok(const void *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k, const void *qsrc,
+                    uint64_t qsrc_size, const void *queries, size_t nq, uint64_t *n_total, uint32_t *filled)
 {
-    if ((nq && !queries) || (k && !levels) || k > ZSCRC_FIND_LEVELS_MAX || (!src && src_size) ||
-        (!qsrc && qsrc_size) || src_size > zspack::SRC_MAX || qsrc_size > zspack::SRC_MAX || nq > N_MAX)
-        return false;
-    uint64_t n = 0;
-    *filled = 0;
-    for (size_t l = 0; l < k; ++l) {
-        if ((levels[l].n && !levels[l].d_recs) || levels[l].n > N_MAX - n)
-            return false;
-        n += levels[l].n;
-        *filled += levels[l].n != 0;
-    }
-    *n_total = n;
-    return true;
+    return !(nq && !queries) && !(!src && src_size) && !(!qsrc && qsrc_size) && src_size <= zspack::SRC_MAX &&
+           qsrc_size <= zspack::SRC_MAX && nq <= N_MAX &&
+           zsdev::lists_ok(levels, k, ZSCRC_FIND_LEVELS_MAX, n_total, filled);
 }
 
-/* The check of the host forms, every record of every level in seq order: the
- * smallest offending seq of each kind (U64_MAX: none) into res[0], [1], [7]
- * as the seal kernels write them; false = an offence. */
-bool host_check(const uint8_t *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k,
-                       bool check_order, uint64_t *res)
+bool host_check(const uint8_t *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k, bool check_order,
+                uint64_t *res)
 {
     uint64_t bad = U64_MAX, order = U64_MAX, seq = 0;
     for (size_t l = 0; l < k; ++l)
@@ -154,12 +124,7 @@ bool host_check(const uint8_t *src, uint64_t src_size, const zscrc_merge_list *l
             if (zsmerge::rebase(prev, levels[l].base, src_size) && order_offence(src, prev, r))
                 order = seq;
         }
-    if (bad == U64_MAX && order == U64_MAX)
-        return true;
-    res[0] = (uint64_t)(int64_t)ZSCRC_EINVAL;
-    res[1] = bad != U64_MAX ? bad : order;
-    res[7] = bad == U64_MAX;
-    return false;
+    return !check_verdict(bad, order, res);
 }
 
 } /* namespace zsfind */
@@ -266,15 +231,10 @@ __global__ void find_seal_kernel(Find a)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0)
         return;
-    const uint64_t bad = a.sc[SC_BAD], order = a.sc[SC_ORDER];
     for (int i = 0; i < ZSCRC_FIND_RES_WORDS; ++i)
         a.res[i] = 0;
-    if (bad != U64_MAX || order != U64_MAX) {
-        a.res[0] = (uint64_t)(int64_t)ZSCRC_EINVAL;
-        a.res[1] = bad != U64_MAX ? bad : order;
-        a.res[7] = bad == U64_MAX;
+    if (check_verdict(a.sc[SC_BAD], a.sc[SC_ORDER], a.res))
         return;
-    }
     a.res[1] = a.nq;
     a.res[2] = a.sc[SC_VALUES];
     a.res[3] = a.sc[SC_DELETES];
@@ -285,51 +245,27 @@ __global__ void find_seal_kernel(Find a)
 
 uint32_t splitters_of(const zscrc_find_opts *o) { return zsfind::splitters_of(o ? o->splitters : 0); }
 
-/* The pieces of the scratch for k levels: the words, the descriptors of the
- * levels and the entry that ends them, a table for every level. */
-struct Plan {
-    size_t levels_at, tabs_at, bytes;
-};
-Plan plan_of(size_t k, uint32_t S)
+/* The scratch of a call with k levels, its pieces into a; the bytes. */
+size_t carve(Find &a, size_t k, zs::Carve c)
 {
-    Plan p;
-    p.levels_at = SC_WORDS * 8;
-    p.tabs_at = p.levels_at + up16((k + 1) * sizeof(LevelD));
-    p.bytes = p.tabs_at + (S > 1 ? k * 4 * (size_t)S * 8 : 0);
-    return p;
+    carve_levels(a, k, c);
+    return up16(c.bytes());
 }
 
-int launch(Find &a, const Plan &p, void *scratch, zs::Scratch &sc, const zscrc_merge_list *levels, size_t k,
-           hipStream_t s)
+int launch(Find &a, void *scratch, zs::Scratch &sc, const zscrc_merge_list *levels, size_t k, hipStream_t s)
 {
-    uint8_t *base = static_cast<uint8_t *>(scratch);
-    a.sc = reinterpret_cast<unsigned long long *>(base);
-    LevelD *d_levels = reinterpret_cast<LevelD *>(base + p.levels_at);
-    a.levels = d_levels;
-    a.tabs = reinterpret_cast<uint64_t *>(base + p.tabs_at);
-    const int rc = launch_levels(a, d_levels, sc, levels, k, s);
+    carve(a, k, zs::Carve(scratch));
+    const int rc = launch_levels(a, sc, levels, k, s);
     if (rc)
         return rc;
     if (a.nq) {
         const uint32_t lds = table_lds(a.S), grid = table_grid(a.S, a.nq);
-        Pass ps{};
-        ps.first = 1;
-        uint32_t li = 0;
-        for (size_t l = 0; l < k; ++l) {
-            if (!levels[l].n)
-                continue;
-            ps.lv = Level{levels[l].d_recs, levels[l].n, levels[l].base};
-            ps.level = l;
-            ps.tab = a.tabs + (uint64_t)li * 4 * a.S;
-            ps.last = ++li == a.filled;
-            ps.last_level = l + 1 == k;
-            hipLaunchKernelGGL(find_search_kernel, dim3(grid), dim3(WG), lds, s, a, ps);
-            ps.first = 0;
-        }
-        if (!a.filled) { /* no level holds a record: the hits and the counts all the same */
-            ps.last = ps.last_level = 1;
-            hipLaunchKernelGGL(find_search_kernel, dim3(grid), dim3(WG), lds, s, a, ps);
-        }
+        for_filled_levels(a, levels, k,
+                          [&](const Level &lv, size_t l, uint32_t, const uint64_t *tab, bool first, bool last) {
+                              /* l = k: no level holds a record, the hits and the counts all the same */
+                              const Pass ps{lv, l, tab, first, last, l + 1 >= k};
+                              hipLaunchKernelGGL(find_search_kernel, dim3(grid), dim3(WG), lds, s, a, ps);
+                          });
     }
     hipLaunchKernelGGL(find_seal_kernel, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError() == hipSuccess ? ZSCRC_OK : ZSCRC_EHIP;
@@ -352,7 +288,11 @@ extern "C" {
 size_t zscrc_device_find_scratch_bytes(size_t k, const zscrc_find_opts *opts)
 {
     const uint32_t S = splitters_of(opts);
-    return S && k <= ZSCRC_FIND_LEVELS_MAX ? plan_of(k, S).bytes : 0;
+    if (!S || k > ZSCRC_FIND_LEVELS_MAX)
+        return 0;
+    Find a{};
+    a.S = S;
+    return carve(a, k, zs::Carve(nullptr));
 }
 
 int zscrc_device_find(const void *d_src, uint64_t src_size, const zscrc_merge_list *levels, size_t k,
@@ -380,10 +320,9 @@ int zscrc_device_find(const void *d_src, uint64_t src_size, const zscrc_merge_li
     a.nq = (uint32_t)nq;
     a.S = S;
     a.check_order = flags & ZSCRC_FIND_CHECK_ORDER;
-    const Plan p = plan_of(k, S);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return zs::with_scratch(scratch, p.bytes, true, s,
-                            [&](void *sp, zs::Scratch *sc) { return launch(a, p, sp, *sc, levels, k, s); });
+    return zs::with_scratch(scratch, carve(a, k, zs::Carve(nullptr)), true, s,
+                            [&](void *sp, zs::Scratch *sc) { return launch(a, sp, *sc, levels, k, s); });
 }
 
 int zscrc_zs_find(const void *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k, const void *qsrc,

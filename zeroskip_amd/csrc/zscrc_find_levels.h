@@ -1,11 +1,12 @@
 /*
  * zscrc_find_levels.h -- what the device lookup (zscrc_find.hip) and the
- * device prefix scan (zscrc_scan.hip) share of their first two launches: the
- * levels as they lie on the device, the check of every level record and the
- * splitter tables, with the host code that stages the descriptors and checks
- * the arguments both entry points take.  The two kernels and the host
- * functions are defined once, in zscrc_find.hip; this header declares them and
- * holds the inline pieces a kernel of either file calls.
+ * device prefix scan (zscrc_scan.hip) share: the levels of a call (descriptors
+ * as zscrc_lists.h stages them), the check of every level record and the
+ * splitter tables, the levels' part of the scratch, the walk over the levels
+ * that are not empty, and the host code that launches the check and the tables
+ * and checks the arguments both entry points take.  The host functions are
+ * defined once, in zscrc_find.hip, with the two kernels they launch; this
+ * header declares them and holds the inline pieces either file calls.
  */
 #ifndef ZSCRC_FIND_LEVELS_H
 #define ZSCRC_FIND_LEVELS_H
@@ -17,10 +18,13 @@
 #include "../../include/zscrc.h"
 #include "zscrc_find_order.h"
 #include "zscrc_internal.h"
+#include "zscrc_lists.h"
 #include "zscrc_wg.h"
 
 namespace zsfind {
 
+using zsdev::Firsts;
+using zsdev::ListD;
 using zsdev::N_MAX;
 using zsdev::WG;
 using zspack::U64_MAX;
@@ -35,20 +39,6 @@ constexpr uint32_t GRID_MAX = 1024;
  * 256 CUs of 160 KiB LDS, each holding 8 workgroups of WG threads */
 constexpr uint32_t CUS = 256, LDS_PER_CU = 160 * 1024, WG_PER_CU = 8;
 
-/* A level on the device: its records, the seq of its first one, its base,
- * its index among the caller's levels.  The entry one past the last level
- * that is not empty holds n_total. */
-struct LevelD {
-    const zscrc_zs_record *recs;
-    uint64_t first;
-    uint64_t base;
-    uint64_t level;
-};
-struct Firsts {
-    const LevelD *d;
-    __host__ __device__ uint64_t operator[](uint64_t i) const { return d[i].first; }
-};
-
 /* scratch words: the two minima of the check, then the caller's counters */
 enum { SC_BAD = 0, SC_ORDER = 1, SC_COUNTERS = 2, SC_WORDS = 16 };
 
@@ -57,7 +47,7 @@ struct Levels {
     const uint8_t *src;
     uint64_t src_size;
     unsigned long long *sc; /* SC_WORDS words */
-    const LevelD *levels;
+    ListD *levels;          /* those that are not empty and the entry that ends them */
     uint64_t *tabs;         /* filled levels x 4 S words */
     uint32_t filled;        /* levels that are not empty */
     uint32_t n;             /* n_total */
@@ -66,12 +56,6 @@ struct Levels {
 };
 
 __device__ inline bool is_bad(const Levels &a) { return (a.sc[SC_BAD] & a.sc[SC_ORDER]) != U64_MAX; }
-
-/* one thread a level record: rebased and checked against the source, with
- * check_order its key against its predecessor's; thread 0 zeroes the counters */
-__global__ void find_check_kernel(Levels a);
-/* one thread a splitter of every level that is not empty */
-__global__ void find_table_kernel(Levels a);
 
 /* A workgroup's copy of one level's table (4 S words) into LDS; S = 1: none. */
 __device__ inline void table_to_lds(uint8_t *lds, const uint64_t *tab, uint32_t S)
@@ -86,10 +70,17 @@ __device__ inline void table_to_lds(uint8_t *lds, const uint64_t *tab, uint32_t 
 }
 
 /* The splitters of a call; 0 = a bad option. */
-inline uint32_t splitters_of(uint32_t asked)
+inline uint32_t splitters_of(uint32_t asked) { return (uint32_t)zsdev::pow2_opt(asked, DEF_SPLITTERS, 1, S_MAX); }
+
+/* The head of the scratch of a call with k levels into a: the words, the
+ * descriptors, a table for every level. */
+inline void carve_levels(Levels &a, size_t k, zs::Carve &c)
 {
-    const uint32_t s = asked ? asked : DEF_SPLITTERS;
-    return zsdev::pow2(s) && s <= S_MAX ? s : 0;
+    a.sc = c.take<unsigned long long>(SC_WORDS, 16);
+    /* 32 bytes a level, as when a descriptor carried its level's index: a ListD
+     * is 24, but the documented size of the scratch stays what callers reserve */
+    a.levels = reinterpret_cast<ListD *>(c.take<uint8_t>((k + 1) * 32, 16));
+    a.tabs = c.take<uint64_t>(a.S > 1 ? k * 4 * (size_t)a.S : 0, 16);
 }
 
 /* The LDS of a launch that searches one level's table, and the workgroups of
@@ -105,10 +96,30 @@ inline uint32_t table_grid(uint32_t S, uint64_t items)
 }
 
 /* The first launches of a call: the descriptors of the levels that hold
- * records to d_levels through the pinned staging, the two minima preset, the
- * check, the tables. */
-int launch_levels(const Levels &a, LevelD *d_levels, zs::Scratch &sc, const zscrc_merge_list *levels, size_t k,
-                  hipStream_t s);
+ * records to a.levels through the pinned staging, the two minima preset, the
+ * check (one thread a level record: rebased and checked against the source,
+ * with check_order its key against its predecessor's; thread 0 zeroes the
+ * counters), the tables (one thread a splitter of every level that is not
+ * empty). */
+int launch_levels(const Levels &a, zs::Scratch &sc, const zscrc_merge_list *levels, size_t k, hipStream_t s);
+
+/* f(level, l, li, tab, first, last) for every level that is not empty: its
+ * index among the caller's and among those, its table, whether it is the first
+ * and the last one.  None holds a record: f once with an empty level, l = k. */
+template <class F>
+inline void for_filled_levels(const Levels &a, const zscrc_merge_list *levels, size_t k, F f)
+{
+    uint32_t li = 0;
+    for (size_t l = 0; l < k; ++l) {
+        if (!levels[l].n)
+            continue;
+        f(Level{levels[l].d_recs, levels[l].n, levels[l].base}, l, li, a.tabs + (uint64_t)li * 4 * a.S, li == 0,
+          li + 1 == a.filled);
+        ++li;
+    }
+    if (!li)
+        f(Level{}, k, 0u, static_cast<const uint64_t *>(nullptr), true, true);
+}
 /* The argument checks of the levels, the sources and the queries that the
  * device and the host entries of the lookup and of the scan share; *n_total
  * and *filled on success. */

@@ -173,6 +173,20 @@ ZSREC_HD inline bool order_offence(const uint8_t *src, const zscrc_zs_record &pr
     return cmp_key(src, make_query(src, prev.key_off, prev.key_len), src, r.key_off, r.key_len) >= 0;
 }
 
+/* The verdict of the check of the levels from its two minima, the smallest seq
+ * of a record outside the source and the smallest one out of order (U64_MAX:
+ * none): false = no offence, res untouched; else res[0] = ZSCRC_EINVAL, res[1]
+ * the seq and res[7] which kind, a record outside the source first. */
+ZSREC_HD inline bool check_verdict(uint64_t bad, uint64_t order, uint64_t *res)
+{
+    if (bad == zspack::U64_MAX && order == zspack::U64_MAX)
+        return false;
+    res[0] = (uint64_t)(int64_t)ZSCRC_EINVAL;
+    res[1] = bad != zspack::U64_MAX ? bad : order;
+    res[7] = bad == zspack::U64_MAX;
+    return true;
+}
+
 } /* namespace zsfind */
 
 #endif

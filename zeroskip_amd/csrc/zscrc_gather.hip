@@ -38,6 +38,9 @@
  * its first half if that is whole and byte stores of the rest -- so the bound
  * of its writes is the total itself, below both the total rounded up to 16
  * and out_cap.
+ *
+ * The sums are zscrc_wg.h's; the scratch is laid out by carve(); the option
+ * rule, the pointer checks and the copy's grid are zsdev's (zscrc_internal.h).
  */
 #include <hip/hip_runtime.h>
 
@@ -92,9 +95,6 @@ struct Gather {
     uint64_t tile;
 };
 
-struct SatAdd {
-    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return sum_len(a, b); }
-};
 struct Max {
     __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a > b ? a : b; }
 };
@@ -212,8 +212,6 @@ struct ItemOffs {
     __device__ uint64_t operator()(uint64_t i) const { return items[i].val_off; }
 };
 
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
 /* The first n (1..16) bytes of the word (v0, v1) to the 16-byte aligned p: one
  * 16-byte store, or for the total's last word an 8-byte store of its first
  * half if that is whole and byte stores of the rest. */
@@ -310,24 +308,26 @@ __global__ __launch_bounds__(WG) void gather_copy_kernel(Gather a)
 }
 
 /* The tile of a call; 0 = a bad option. */
-uint64_t tile_of(const zscrc_gather_opts *o)
+uint64_t tile_of(const zscrc_gather_opts *o) { return pow2_opt(o ? o->tile_bytes : 0, DEF_TILE, TILE_MIN, TILE_MAX); }
+
+/* The pieces of the scratch into a, one 8-byte array behind the other; the bytes. */
+size_t carve(Gather &a, zs::Carve c)
 {
-    const uint64_t t = o && o->tile_bytes ? o->tile_bytes : DEF_TILE;
-    return pow2(t) && t >= TILE_MIN && t <= TILE_MAX ? t : 0;
+    a.nblocks = blocks_of(a.nq);
+    a.sc = c.take<unsigned long long>(SC_WORDS, 16);
+    a.bsum = c.take<uint64_t>(a.nblocks + 1);
+    a.clen = c.take<uint64_t>(a.nq);
+    a.coff = c.take<uint64_t>(a.nq);
+    return up16(c.bytes());
 }
-
-uint64_t blocks_of(uint64_t n) { return (n + BLOCK_RECS - 1) / BLOCK_RECS; }
-
-size_t scratch_need(uint64_t nq) { return up16((size_t)((SC_WORDS + blocks_of(nq) + 1 + 2 * nq) * 8)); }
 
 int launch(Gather &a, void *scratch, uint32_t *d_crcs, hipStream_t s)
 {
-    a.sc = static_cast<unsigned long long *>(scratch);
-    a.bsum = reinterpret_cast<uint64_t *>(a.sc) + SC_WORDS;
+    carve(a, zs::Carve(scratch));
     const bool sizing = !a.out && !a.out_cap;
     const bool crcs = d_crcs && !sizing && a.nq;
-    a.clen = crcs ? a.bsum + a.nblocks + 1 : nullptr;
-    a.coff = crcs ? a.clen + a.nq : nullptr;
+    if (!crcs)
+        a.clen = a.coff = nullptr;
     if (a.nq) {
         if (hipMemsetAsync(a.sc + SC_BAD, 0xFF, 8, s) != hipSuccess ||
             hipMemsetAsync(a.sc + SC_KIND, 0, (SC_WORDS - SC_KIND) * 8, s) != hipSuccess)
@@ -340,21 +340,15 @@ int launch(Gather &a, void *scratch, uint32_t *d_crcs, hipStream_t s)
     if (hipGetLastError() != hipSuccess)
         return ZSCRC_EHIP;
     if (a.nq && a.out_cap) {
-        int dev = 0, ncu = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
+        /* the total is on the device only */
+        unsigned g;
+        if (copy_grid(a.out_cap, a.tile, COPY_WG_PER_CU, &g) != ZSCRC_OK)
             return ZSCRC_EHIP;
-        /* the total is on the device only: a grid for the most the output can
-         * hold, capped; a workgroup takes a run of the tiles there are */
-        uint64_t g = (a.out_cap + a.tile - 1) / a.tile;
-        const uint64_t gmax = (uint64_t)ncu * COPY_WG_PER_CU;
-        if (g > gmax)
-            g = gmax;
         const char *search = getenv("ZSCRC_GATHER_SEARCH");
         if (search && search[0] == '1')
-            hipLaunchKernelGGL(gather_copy_search_kernel, dim3((unsigned)g), dim3(WG), 0, s, a);
+            hipLaunchKernelGGL(gather_copy_search_kernel, dim3(g), dim3(WG), 0, s, a);
         else
-            hipLaunchKernelGGL(gather_copy_kernel, dim3((unsigned)g), dim3(WG), 0, s, a);
+            hipLaunchKernelGGL(gather_copy_kernel, dim3(g), dim3(WG), 0, s, a);
         if (hipGetLastError() != hipSuccess)
             return ZSCRC_EHIP;
     }
@@ -373,7 +367,9 @@ size_t zscrc_device_gather_scratch_bytes(size_t nq, const zscrc_gather_opts *opt
 {
     if (!tile_of(opts) || nq > N_MAX)
         return 0;
-    return scratch_need(nq);
+    Gather a{};
+    a.nq = nq;
+    return carve(a, zs::Carve(nullptr));
 }
 
 int zscrc_device_gather(const void *d_src, uint64_t src_size, const zscrc_find_hit *d_items, size_t nq, void *d_out,
@@ -382,13 +378,9 @@ int zscrc_device_gather(const void *d_src, uint64_t src_size, const zscrc_find_h
 {
     static_assert(sizeof(Item) == sizeof(zscrc_find_hit) && sizeof(Item) == sizeof(zscrc_zs_record),
                   "an item is four words");
-    const uintptr_t so = reinterpret_cast<uintptr_t>(d_src), oo = reinterpret_cast<uintptr_t>(d_out);
     const uint64_t tile = tile_of(opts);
-    if (!d_res || !d_offs || (nq && !d_items) || (!d_src && src_size) || (out_cap && !d_out) || (oo & 15) ||
-        (reinterpret_cast<uintptr_t>(scratch) & 15) || flags || !tile || nq > N_MAX || src_size > zspack::SRC_MAX ||
-        out_cap > UINTPTR_MAX - oo || src_size > UINTPTR_MAX - so)
-        return ZSCRC_EINVAL;
-    if (out_cap && src_size && oo < so + src_size && so < oo + out_cap)
+    if (!d_res || !d_offs || (nq && !d_items) || (reinterpret_cast<uintptr_t>(scratch) & 15) || flags || !tile ||
+        nq > N_MAX || src_size > zspack::SRC_MAX || !src_out_ok(d_src, src_size, d_out, out_cap, true))
         return ZSCRC_EINVAL;
     Gather a{};
     a.src = static_cast<const uint8_t *>(d_src);
@@ -399,21 +391,17 @@ int zscrc_device_gather(const void *d_src, uint64_t src_size, const zscrc_find_h
     a.out_cap = out_cap;
     a.offs = d_offs;
     a.res = d_res;
-    a.nblocks = blocks_of(nq);
     a.tile = tile;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return zs::with_scratch(scratch, scratch_need(nq), false, s,
+    return zs::with_scratch(scratch, carve(a, zs::Carve(nullptr)), false, s,
                             [&](void *p, zs::Scratch *) { return launch(a, p, d_crcs, s); });
 }
 
 int zscrc_zs_gather(const void *src, uint64_t src_size, const zscrc_find_hit *items, size_t nq, void *out,
                     uint64_t out_cap, uint64_t *offs, uint32_t *crcs, uint64_t res[ZSCRC_GATHER_RES_WORDS])
 {
-    const uintptr_t so = reinterpret_cast<uintptr_t>(src), oo = reinterpret_cast<uintptr_t>(out);
-    if (!res || !offs || (nq && !items) || (!src && src_size) || (out_cap && !out) || nq > N_MAX ||
-        src_size > zspack::SRC_MAX || out_cap > UINTPTR_MAX - oo || src_size > UINTPTR_MAX - so)
-        return ZSCRC_EINVAL;
-    if (out_cap && src_size && oo < so + src_size && so < oo + out_cap)
+    if (!res || !offs || (nq && !items) || nq > N_MAX || src_size > zspack::SRC_MAX ||
+        !src_out_ok(src, src_size, out, out_cap, false))
         return ZSCRC_EINVAL;
     const uint8_t *s = static_cast<const uint8_t *>(src);
     uint8_t *o = static_cast<uint8_t *>(out);

@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "../../include/zscrc.h"
+#include "zscrc_carve.h"
 
 /* Global operator-table block (uint32 words), built on the host per device. */
 enum {
@@ -478,18 +479,45 @@ struct SpanFolds {
 
 } /* namespace zs */
 
-/* What the device stages (zscrc_walk.hip, zscrc_devpack.hip, zscrc_merge.hip)
- * share on host and device; their workgroup primitives: zscrc_wg.h. */
+/* What the device stages (zscrc_walk.hip, zscrc_devpack.hip, zscrc_merge.hip,
+ * zscrc_find.hip, zscrc_gather.hip, zscrc_scan.hip) share on host and device;
+ * their workgroup primitives: zscrc_wg.h, the scratch layout of a call:
+ * zs::Carve (zscrc_carve.h), the staged list descriptors: zscrc_lists.h. */
 namespace zsdev {
 
 constexpr int WG = 256;
-/* the packer and the merge cut a record list into blocks, one workgroup each */
+/* the packer, the merge, the gather and the scan cut a list into blocks, one
+ * workgroup each */
 constexpr uint32_t PER = 4;                  /* records a thread of a block */
 constexpr uint32_t BLOCK_RECS = WG * PER;
 constexpr uint64_t N_MAX = (1ull << 31) - 1; /* records of one call */
 
 constexpr bool pow2(uint64_t v) { return v && !(v & (v - 1)); }
 constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+constexpr uint64_t blocks_of(uint64_t n) { return (n + BLOCK_RECS - 1) / BLOCK_RECS; }
+
+/* An option that is a power of two in [min, max]: 0 asks for the default, and
+ * 0 returned = a bad option. */
+constexpr uint64_t pow2_opt(uint64_t asked, uint64_t def, uint64_t min, uint64_t max)
+{
+    const uint64_t v = asked ? asked : def;
+    return pow2(v) && v >= min && v <= max ? v : 0;
+}
+
+/* The source and the output of a call: no NULL with a size, no range that
+ * wraps, no overlap; align16: the output on a 16-byte boundary. */
+inline bool src_out_ok(const void *src, uint64_t src_size, const void *out, uint64_t out_cap, bool align16)
+{
+    const uintptr_t so = reinterpret_cast<uintptr_t>(src), oo = reinterpret_cast<uintptr_t>(out);
+    if ((!src && src_size) || (!out && out_cap) || (align16 && (oo & 15)) || out_cap > UINTPTR_MAX - oo ||
+        src_size > UINTPTR_MAX - so)
+        return false;
+    return !(out_cap && src_size && oo < so + src_size && so < oo + out_cap);
+}
+
+/* The grid of a tiled copy whose byte count is on the device only: a workgroup
+ * a tile the output can hold, at most wg_per_cu a CU; each takes a run of tiles. */
+int copy_grid(uint64_t out_cap, uint64_t tile, unsigned wg_per_cu, unsigned *grid);
 
 } /* namespace zsdev */
 

@@ -32,8 +32,9 @@
  * record makes every launch after the gather return at once.
  *
  * The sums and prefix sums are zscrc_wg.h's (merge_scan_kernel: scan_counts);
- * the scratch of a call and the pinned staging of the list descriptors come
- * through zs::with_scratch (zscrc_internal.h, zscrc_scratch.cpp).
+ * the list descriptors, their check and their staging are zscrc_lists.h's; the
+ * scratch of a call comes through zs::with_scratch (zscrc_internal.h,
+ * zscrc_scratch.cpp), laid out by carve().
  */
 #include <hip/hip_runtime.h>
 
@@ -42,6 +43,7 @@
 
 #include "../../include/zscrc.h"
 #include "zscrc_internal.h"
+#include "zscrc_lists.h"
 #include "zscrc_merge_order.h"
 #include "zscrc_wg.h"
 
@@ -55,25 +57,13 @@ using zspack::U64_MAX;
  * 1,024, shuffled input 21 % faster) */
 constexpr uint32_t DEF_TILE = 2048, TILE_MIN = 64, TILE_MAX = 2048;
 
-/* A list on the device: its records, the seq of its first one, its base.
- * Entry k (one past the last list) holds n_total. */
-struct ListD {
-    const zscrc_zs_record *recs;
-    uint64_t first;
-    uint64_t base;
-};
-struct Firsts {
-    const ListD *d;
-    __host__ __device__ uint64_t operator[](uint64_t i) const { return d[i].first; }
-};
-
 /* scratch words */
 enum { SC_BAD = 0, SC_DELETES = 1, SC_SUMK = 2, SC_SUMV = 3, SC_DROPPED = 4, SC_WORDS = 16 };
 
 struct Merge {
     const uint8_t *src;
     uint64_t src_size;
-    const ListD *lists;
+    ListD *lists;      /* those that are not empty and the entry that ends them */
     uint32_t k;        /* lists that are not empty */
     uint32_t n;        /* n_total */
     uint32_t tile;
@@ -297,63 +287,31 @@ __global__ __launch_bounds__(WG) void merge_scatter_kernel(Merge a)
 /* The tile of a call; 0 = a bad option. */
 uint32_t tile_of(const zscrc_merge_opts *o)
 {
-    const uint32_t t = o && o->tile_records ? o->tile_records : DEF_TILE;
-    return pow2(t) && t >= TILE_MIN && t <= TILE_MAX ? t : 0;
+    return (uint32_t)pow2_opt(o ? o->tile_records : 0, DEF_TILE, TILE_MIN, TILE_MAX);
 }
 
-/* The pieces of the scratch for n records: the words, the descriptors of at
- * most min(n, ZSCRC_WALK_MULTI_MAX) lists that are not empty and the entry
- * that ends them, the rebased records, two entry arrays, the block counts,
- * the flags. */
-struct Plan {
-    size_t lists_at, rb_at, e0_at, e1_at, bcount_at, flags_at, bytes;
-    uint32_t nblocks;
-};
-Plan plan_of(uint64_t n)
+/* The pieces of the scratch into a, each on a 16-byte boundary (at most min(n,
+ * ZSCRC_WALK_MULTI_MAX) lists are not empty); the bytes. */
+size_t carve(Merge &a, zs::Carve c)
 {
-    Plan p;
-    const uint64_t kmax = n < ZSCRC_WALK_MULTI_MAX ? n : ZSCRC_WALK_MULTI_MAX;
-    p.nblocks = (uint32_t)((n + BLOCK_RECS - 1) / BLOCK_RECS);
-    p.lists_at = SC_WORDS * 8;
-    p.rb_at = p.lists_at + up16((kmax + 1) * sizeof(ListD));
-    p.e0_at = p.rb_at + n * sizeof(zscrc_zs_record);
-    p.e1_at = p.e0_at + n * sizeof(Entry);
-    p.bcount_at = p.e1_at + n * sizeof(Entry);
-    p.flags_at = p.bcount_at + up16((p.nblocks + 1) * 4);
-    p.bytes = p.flags_at + up16(n);
-    return p;
+    const size_t n = a.n, kmax = n < ZSCRC_WALK_MULTI_MAX ? n : ZSCRC_WALK_MULTI_MAX;
+    a.nblocks = (uint32_t)blocks_of(n);
+    a.sc = c.take<unsigned long long>(SC_WORDS, 16);
+    a.lists = c.take<ListD>(kmax + 1, 16);
+    a.rb = c.take<zscrc_zs_record>(n, 16);
+    a.e0 = c.take<Entry>(n, 16);
+    a.e1 = c.take<Entry>(n, 16);
+    a.bcount = c.take<uint32_t>(a.nblocks + 1, 16);
+    a.flags = c.take<uint8_t>(n, 16);
+    return up16(c.bytes());
 }
 
-int launch(Merge &a, const Plan &p, void *scratch, zs::Scratch &sc, const zscrc_merge_list *lists, size_t k,
-           hipStream_t s)
+int launch(Merge &a, void *scratch, zs::Scratch &sc, const zscrc_merge_list *lists, size_t k, hipStream_t s)
 {
-    uint8_t *base = static_cast<uint8_t *>(scratch);
-    a.sc = reinterpret_cast<unsigned long long *>(base);
-    ListD *d_lists = reinterpret_cast<ListD *>(base + p.lists_at);
-    a.lists = d_lists;
-    a.rb = reinterpret_cast<zscrc_zs_record *>(base + p.rb_at);
-    a.e0 = reinterpret_cast<Entry *>(base + p.e0_at);
-    a.e1 = reinterpret_cast<Entry *>(base + p.e1_at);
-    a.bcount = reinterpret_cast<uint32_t *>(base + p.bcount_at);
-    a.flags = base + p.flags_at;
-    a.nblocks = p.nblocks;
+    carve(a, zs::Carve(scratch));
     a.sorted = a.e0;
     if (a.n) {
-        /* the descriptors of the lists that hold records, through the pinned staging */
-        const size_t bytes = ((size_t)a.k + 1) * sizeof(ListD);
-        int rc = zs::stage_begin(sc, bytes);
-        if (rc)
-            return rc;
-        ListD *h = static_cast<ListD *>(sc.pin);
-        uint64_t first = 0;
-        for (size_t l = 0; l < k; ++l) {
-            if (!lists[l].n)
-                continue;
-            *h++ = ListD{lists[l].d_recs, first, lists[l].base};
-            first += lists[l].n;
-        }
-        *h = ListD{nullptr, first, 0};
-        rc = zs::stage_copy(sc, d_lists, bytes, s);
+        const int rc = stage_lists(sc, lists, k, a.k, a.lists, s);
         if (rc)
             return rc;
         if (hipMemsetAsync(a.sc, 0, SC_WORDS * 8, s) != hipSuccess ||
@@ -387,7 +345,9 @@ size_t zscrc_device_merge_scratch_bytes(size_t n_total, const zscrc_merge_opts *
 {
     if (!tile_of(opts) || n_total > N_MAX)
         return 0;
-    return plan_of(n_total).bytes;
+    Merge a{};
+    a.n = (uint32_t)n_total;
+    return carve(a, zs::Carve(nullptr));
 }
 
 int zscrc_device_merge(const void *d_src, uint64_t src_size, const zscrc_merge_list *lists, size_t k,
@@ -395,33 +355,25 @@ int zscrc_device_merge(const void *d_src, uint64_t src_size, const zscrc_merge_l
                        const zscrc_merge_opts *opts, unsigned flags, void *stream)
 {
     const uint32_t tile = tile_of(opts);
-    if (!d_res || (k && !lists) || (!d_src && src_size) || (cap && !d_out) ||
-        (reinterpret_cast<uintptr_t>(scratch) & 15) || (flags & ~ZSCRC_MERGE_DROP_DELETES) || !tile ||
-        k > ZSCRC_WALK_MULTI_MAX || src_size > zspack::SRC_MAX)
+    uint64_t n = 0;
+    uint32_t filled = 0;
+    if (!d_res || (!d_src && src_size) || (cap && !d_out) || (reinterpret_cast<uintptr_t>(scratch) & 15) ||
+        (flags & ~ZSCRC_MERGE_DROP_DELETES) || !tile || src_size > zspack::SRC_MAX ||
+        !lists_ok(lists, k, ZSCRC_WALK_MULTI_MAX, &n, &filled))
         return ZSCRC_EINVAL;
-    uint64_t n = 0, filled = 0;
-    for (size_t l = 0; l < k; ++l) {
-        if (lists[l].n && !lists[l].d_recs)
-            return ZSCRC_EINVAL;
-        if (lists[l].n > N_MAX - n)
-            return ZSCRC_EINVAL;
-        n += lists[l].n;
-        filled += lists[l].n != 0;
-    }
     Merge a{};
     a.src = static_cast<const uint8_t *>(d_src);
     a.src_size = src_size;
-    a.k = (uint32_t)filled;
+    a.k = filled;
     a.n = (uint32_t)n;
     a.tile = tile;
     a.drop = flags & ZSCRC_MERGE_DROP_DELETES;
     a.out = d_out;
     a.cap = cap;
     a.res = d_res;
-    const Plan p = plan_of(n);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return zs::with_scratch(scratch, p.bytes, true, s,
-                            [&](void *sp, zs::Scratch *sc) { return launch(a, p, sp, *sc, lists, k, s); });
+    return zs::with_scratch(scratch, carve(a, zs::Carve(nullptr)), true, s,
+                            [&](void *sp, zs::Scratch *sc) { return launch(a, sp, *sc, lists, k, s); });
 }
 
 } /* extern "C" */

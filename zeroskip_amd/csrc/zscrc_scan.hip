@@ -7,12 +7,13 @@
  * on the device"); zscrc_zs_scan is the same scan in host memory, by a merge
  * with one cursor a level.  The arithmetic is zscrc_scan_order.h's on top of
  * zscrc_find_order.h's search and zscrc_merge_order.h's order, all shared with
- * the host; the check of the levels and their splitter tables are the
- * lookup's (zscrc_find_levels.h).
+ * the host; the check of the levels, their splitter tables, their part of the
+ * scratch and the walk over those that are not empty are the lookup's
+ * (zscrc_find_levels.h).
  *
  * Launches, all in stream order, no workgroup waiting for another one:
  *
- *   find_check_kernel, find_table_kernel      as in zscrc_find.hip
+ *   find_check_kernel, find_table_kernel      zscrc_find.hip's, by launch_levels
  *   scan_bounds_kernel    once per level that is not empty, persistent
  *                         workgroups with a grid-stride loop over the queries
  *                         and the level's table in LDS: the prefix's lower
@@ -96,7 +97,7 @@ __device__ inline bool is_over(const Scan &a) { return is_bad(a) || a.sc[SC_C] >
 
 __device__ inline Level level_of(const Scan &a, uint32_t li)
 {
-    const LevelD l = a.levels[li];
+    const ListD l = a.levels[li];
     return Level{l.recs, a.levels[li + 1].first - l.first, l.base};
 }
 
@@ -337,15 +338,10 @@ __global__ void scan_seal_kernel(Scan a)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0)
         return;
-    const uint64_t bad = a.sc[SC_BAD], order = a.sc[SC_ORDER];
     for (int i = 0; i < ZSCRC_SCAN_RES_WORDS; ++i)
         a.res[i] = 0;
-    if (bad != U64_MAX || order != U64_MAX) {
-        a.res[0] = (uint64_t)(int64_t)ZSCRC_EINVAL;
-        a.res[1] = bad != U64_MAX ? bad : order;
-        a.res[7] = bad == U64_MAX;
+    if (check_verdict(a.sc[SC_BAD], a.sc[SC_ORDER], a.res))
         return;
-    }
     const uint64_t C = a.sc[SC_C];
     a.res[1] = a.nq;
     a.res[3] = C;
@@ -364,58 +360,34 @@ __global__ void scan_seal_kernel(Scan a)
     a.res[9] = a.sc[SC_SUMV];
 }
 
-/* The pieces of the scratch: the words, the descriptors of the levels and the
- * entry that ends them, a table for every level, the matrix's lower bounds
- * and prefix sums with their block sums, the slots with theirs. */
-struct Plan {
-    size_t levels_at, tabs_at, lo_at, start_at, bs1_at, slots_at, bs2_at, bytes;
-};
-Plan plan_of(size_t nq, size_t k, size_t cand_cap, uint32_t S)
+/* The pieces of the scratch into a, each on a 16-byte boundary; the bytes.
+ * The (query, level) matrix is sized for k levels, filled or not. */
+size_t carve(Scan &a, size_t k, zs::Carve c)
 {
-    const size_t pairs = nq * k;
-    Plan p;
-    p.levels_at = SC_WORDS * 8;
-    p.tabs_at = p.levels_at + up16((k + 1) * sizeof(LevelD));
-    p.lo_at = p.tabs_at + (S > 1 ? k * 4 * (size_t)S * 8 : 0);
-    p.start_at = p.lo_at + up16(pairs * 4);
-    p.bs1_at = p.start_at + up16((pairs + 1) * 8);
-    p.slots_at = p.bs1_at + up16((pairs / BLOCK_RECS + 1) * 8);
-    p.bs2_at = p.slots_at + up16(cand_cap * 4);
-    p.bytes = p.bs2_at + up16((cand_cap / BLOCK_RECS + 1) * 8);
-    return p;
+    const size_t pairs = (size_t)a.nq * k;
+    carve_levels(a, k, c);
+    a.lo = c.take<uint32_t>(pairs, 16);
+    a.start = c.take<uint64_t>(pairs + 1, 16);
+    a.bs1 = c.take<uint64_t>(pairs / BLOCK_RECS + 1, 16);
+    a.slots = c.take<uint32_t>(a.cand_cap, 16);
+    a.bs2 = c.take<uint64_t>(a.cand_cap / BLOCK_RECS + 1, 16);
+    return up16(c.bytes());
 }
 
-int launch(Scan &a, const Plan &p, void *scratch, zs::Scratch &sc, const zscrc_merge_list *levels, size_t k,
-           hipStream_t s)
+int launch(Scan &a, void *scratch, zs::Scratch &sc, const zscrc_merge_list *levels, size_t k, hipStream_t s)
 {
-    uint8_t *base = static_cast<uint8_t *>(scratch);
-    a.sc = reinterpret_cast<unsigned long long *>(base);
-    LevelD *d_levels = reinterpret_cast<LevelD *>(base + p.levels_at);
-    a.levels = d_levels;
-    a.tabs = reinterpret_cast<uint64_t *>(base + p.tabs_at);
-    a.lo = reinterpret_cast<uint32_t *>(base + p.lo_at);
-    a.start = reinterpret_cast<uint64_t *>(base + p.start_at);
-    a.bs1 = reinterpret_cast<uint64_t *>(base + p.bs1_at);
-    a.slots = reinterpret_cast<uint32_t *>(base + p.slots_at);
-    a.bs2 = reinterpret_cast<uint64_t *>(base + p.bs2_at);
-    const int rc = launch_levels(a, d_levels, sc, levels, k, s);
+    carve(a, k, zs::Carve(scratch));
+    const int rc = launch_levels(a, sc, levels, k, s);
     if (rc)
         return rc;
     if (a.nq) {
         const uint32_t lds = table_lds(a.S), grid = table_grid(a.S, a.nq);
-        Pass ps{};
-        ps.first = 1;
-        for (size_t l = 0; l < k; ++l) {
-            if (!levels[l].n)
-                continue;
-            ps.lv = Level{levels[l].d_recs, levels[l].n, levels[l].base};
-            ps.tab = a.tabs + (uint64_t)ps.li * 4 * a.S;
-            hipLaunchKernelGGL(scan_bounds_kernel, dim3(grid), dim3(WG), lds, s, a, ps);
-            ++ps.li;
-            ps.first = 0;
-        }
-        if (!a.filled) /* no level holds a record: the bad queries all the same */
-            hipLaunchKernelGGL(scan_bounds_kernel, dim3(grid), dim3(WG), lds, s, a, ps);
+        for_filled_levels(a, levels, k,
+                          [&](const Level &lv, size_t, uint32_t li, const uint64_t *tab, bool first, bool) {
+                              /* an empty level: none holds a record, the bad queries all the same */
+                              const Pass ps{lv, tab, li, first};
+                              hipLaunchKernelGGL(scan_bounds_kernel, dim3(grid), dim3(WG), lds, s, a, ps);
+                          });
     }
     const uint32_t pair_blocks = (uint32_t)((a.pairs + BLOCK_RECS - 1) / BLOCK_RECS);
     if (pair_blocks)
@@ -456,7 +428,13 @@ extern "C" {
 size_t zscrc_device_scan_scratch_bytes(size_t nq, size_t k, size_t cand_cap, const zscrc_scan_opts *opts)
 {
     const uint32_t S = splitters_of(opts ? opts->splitters : 0);
-    return S && k <= ZSCRC_FIND_LEVELS_MAX && nq <= N_MAX && cand_cap <= N_MAX ? plan_of(nq, k, cand_cap, S).bytes : 0;
+    if (!S || k > ZSCRC_FIND_LEVELS_MAX || nq > N_MAX || cand_cap > N_MAX)
+        return 0;
+    Scan a{};
+    a.S = S;
+    a.nq = (uint32_t)nq;
+    a.cand_cap = (uint32_t)cand_cap;
+    return carve(a, k, zs::Carve(nullptr));
 }
 
 int zscrc_device_scan(const void *d_src, uint64_t src_size, const zscrc_merge_list *levels, size_t k,
@@ -490,10 +468,9 @@ int zscrc_device_scan(const void *d_src, uint64_t src_size, const zscrc_merge_li
     a.keep = flags & ZSCRC_SCAN_KEEP_DELETES;
     a.S = S;
     a.check_order = flags & ZSCRC_SCAN_CHECK_ORDER;
-    const Plan p = plan_of(nq, k, cand_cap, S);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return zs::with_scratch(scratch, p.bytes, true, s,
-                            [&](void *sp, zs::Scratch *sc) { return launch(a, p, sp, *sc, levels, k, s); });
+    return zs::with_scratch(scratch, carve(a, k, zs::Carve(nullptr)), true, s,
+                            [&](void *sp, zs::Scratch *sc) { return launch(a, sp, *sc, levels, k, s); });
 }
 
 int zscrc_zs_scan(const void *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k, const void *qsrc,

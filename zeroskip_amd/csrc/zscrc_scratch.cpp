@@ -4,7 +4,9 @@
  * device, shared by every call there that passes no scratch of its own
  * (zscrc_device_walk, _records, _walk_multi, _pack, _merge).  A call on another
  * stream than the last user's waits for that user's work.  The calls reach it
- * through zs::with_scratch (zscrc_internal.h).
+ * through zs::with_scratch (zscrc_internal.h).  Also the host code the stages
+ * share that calls HIP: the check and the staging of a call's record lists
+ * (zscrc_lists.h) and the grid of the tiled copies (zsdev::copy_grid).
  */
 #include <hip/hip_runtime.h>
 
@@ -12,6 +14,7 @@
 
 #include "../../include/zscrc.h"
 #include "zscrc_internal.h"
+#include "zscrc_lists.h"
 
 namespace {
 
@@ -93,6 +96,57 @@ int stage_copy(Scratch &sc, void *d_dst, size_t bytes, hipStream_t s)
 }
 
 } /* namespace zs */
+
+/* zscrc_lists.h, and the grid of the tiled copies (zscrc_internal.h) */
+namespace zsdev {
+
+bool lists_ok(const zscrc_merge_list *lists, size_t k, size_t kmax, uint64_t *n_total, uint32_t *filled)
+{
+    if ((k && !lists) || k > kmax)
+        return false;
+    uint64_t n = 0;
+    *filled = 0;
+    for (size_t l = 0; l < k; ++l) {
+        if ((lists[l].n && !lists[l].d_recs) || lists[l].n > N_MAX - n)
+            return false;
+        n += lists[l].n;
+        *filled += lists[l].n != 0;
+    }
+    *n_total = n;
+    return true;
+}
+
+int stage_lists(zs::Scratch &sc, const zscrc_merge_list *lists, size_t k, uint32_t filled, ListD *d_dst,
+                hipStream_t s)
+{
+    const size_t bytes = ((size_t)filled + 1) * sizeof(ListD);
+    const int rc = zs::stage_begin(sc, bytes);
+    if (rc)
+        return rc;
+    ListD *h = static_cast<ListD *>(sc.pin);
+    uint64_t first = 0;
+    for (size_t l = 0; l < k; ++l) {
+        if (!lists[l].n)
+            continue;
+        *h++ = ListD{lists[l].d_recs, first, lists[l].base};
+        first += lists[l].n;
+    }
+    *h = ListD{nullptr, first, 0};
+    return zs::stage_copy(sc, d_dst, bytes, s);
+}
+
+int copy_grid(uint64_t out_cap, uint64_t tile, unsigned wg_per_cu, unsigned *grid)
+{
+    int dev = 0, ncu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
+        return ZSCRC_EHIP;
+    const uint64_t g = (out_cap + tile - 1) / tile, gmax = (uint64_t)ncu * wg_per_cu;
+    *grid = (unsigned)(g < gmax ? g : gmax);
+    return ZSCRC_OK;
+}
+
+} /* namespace zsdev */
 
 /* zscrc_release_cache(): the scratch and the staging, every device. */
 extern "C" void zs_walk_release_cache(void)

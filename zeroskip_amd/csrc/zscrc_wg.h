@@ -1,12 +1,13 @@
 /*
  * zscrc_wg.h -- the workgroup primitives of the device stages (zscrc_walk.hip,
- * zscrc_devpack.hip, zscrc_merge.hip): a sum, an exclusive prefix sum and the
- * one-workgroup scan of a long array of counts.  Device code only, for
- * workgroups of WG = 256 threads in waves of 64.
+ * zscrc_devpack.hip, zscrc_merge.hip, zscrc_find.hip, zscrc_gather.hip,
+ * zscrc_scan.hip): a sum, an exclusive prefix sum and the one-workgroup scan of
+ * a long array of counts, and the 16-byte word of the tiled copies.  Device
+ * code only, for workgroups of WG = 256 threads in waves of 64.
  *
  * Every function takes s, WG / 64 words of LDS that are free again on return,
  * is called by all threads of the workgroup, and takes the addition as a
- * functor: plain + (Plus) or one that saturates (the packer's zspack::sat_add).
+ * functor: plain + (Plus) or one that saturates (SatAdd, for sums of lengths).
  * An addition must be associative and commutative with 0 as its identity.
  */
 #ifndef ZSCRC_WG_H
@@ -17,13 +18,21 @@
 #include <stdint.h>
 
 #include "zscrc_internal.h"
+#include "zscrc_pack_layout.h"
 
 namespace zsdev {
+
+/* two words stored as one aligned 16-byte word (pack_copy_kernel, gather's store_word) */
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
 constexpr uint32_t SCAN_PER = 4; /* scan_counts: counts a thread and chunk */
 
 struct Plus {
     __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a + b; }
+};
+/* Sums of lengths saturate (zscrc_pack_layout.h, zscrc_gather_layout.h's sum_len). */
+struct SatAdd {
+    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return zspack::sat_add(a, b); }
 };
 
 /* Sum of one value a thread over the workgroup, in every thread. */
