@@ -737,6 +737,127 @@ int zscrc_device_pack(const void *d_src, uint64_t src_size,
                       void *d_out, uint64_t out_cap, uint64_t *d_res, void *scratch,
                       const zscrc_pack_opts *opts, unsigned flags, void *stream);
 
+/* The log writer on the device: what zsdb_add / zsdb_remove / zsdb_commit
+ * append to the active file (src/zeroskip.c:863-1004), for a batch of puts and
+ * deletes whose record list and bytes live in device memory -- the write path
+ * in front of zscrc_device_records, without the batch crossing PCIe.  d_out
+ * receives exactly the bytes the format oracle's FileWriter (oracle/
+ * zs_format.py:127-166) builds for the same adds, removes and commits: key
+ * records (long above 65,535 bytes), value records (long above 16,777,215),
+ * delete records, the padding to 8 bytes, and behind each transaction its
+ * commit record.
+ * Records: d_recs[i] is a 32-byte entry as every lister, merge, find or scan of
+ * this library writes it: key_off / val_off are offsets into d_src, val_off ==
+ * ZSCRC_ZS_DELETED a delete (val_len ignored).  Records are written in the
+ * caller's order; they may repeat and share or overlap source bytes.  Record
+ * headers are generated from the lengths, never copied.  A delete whose key is
+ * longer than 65,535 bytes is a bad record: such a log cannot be walked.
+ * Transactions: d_tx_end is a device array of n_tx exclusive end indices,
+ * transaction t = records [d_tx_end[t - 1], d_tx_end[t]) (from 0 for t = 0).
+ * The array is non-decreasing, an entry equal to its predecessor is an empty
+ * transaction (which still gets its commit), and the last entry is n; it is
+ * checked on the device.  d_tx_end == NULL with n_tx == 0: one transaction a
+ * record (add, commit, add, commit ...), n commits.  d_tx_end != NULL with
+ * n_tx == 0: no transaction at all, legal only for n == 0 (for n > 0 entry 0,
+ * the missing last entry, is the bad one).
+ * Span: the CRC span of a commit is the reference's crc32_begin rule
+ * (zeroskip.c:930-931: an add begins it where none is open; :985: a remove
+ * begins it always): it starts at the transaction's LAST delete record if it
+ * has one, else at its first record, and ends at the commit record.  An empty
+ * transaction has a span of no bytes with CRC 0.  The commit record is the
+ * 24-byte long form where the span exceeds 16,777,215 bytes, else 8 bytes.
+ * Position: d_out is the image's base (16-byte aligned), out_cap its capacity.
+ * at == 0 writes the 40-byte header from uuid, startidx, endidx, then the
+ * records from offset 40.  at >= 40, a multiple of 8, appends at file offset at:
+ * no byte of [0, at) is read or written, and uuid, startidx, endidx are ignored.
+ * No byte at or past the end offset is written.  [d_out + at, d_out + out_cap)
+ * must not overlap the source; d_src may lie inside [d_out, d_out + at), so
+ * records can be logged again from the log itself.
+ * ZSCRC_LOG_FINALISE: behind the last transaction, what zs_active_file_finalise
+ * writes when no transaction is open (FileWriter.finalise): a short commit of
+ * no bytes hashed from the CRC of the PREVIOUS span, the stale register of
+ * src/mfile.c:534-546.  The previous span is this call's last transaction;
+ * where the call has none (n_tx == 0 with d_tx_end != NULL) it is
+ * opts->prev_crc (default 0, the xcalloc'd register of a fresh file), which a
+ * chain of calls takes from the earlier call's d_res[6].
+ * Launches in stream order (per-block lengths and delete marks, one
+ * workgroup's scan, the record prefixes, the transactions' spans, one
+ * workgroup's scan and the result, the commit prefixes, the record starts, the
+ * tiled copy in file coordinates, the library's variable-length batch over the
+ * spans, one thread a commit that seals); no workgroup waits for another, and
+ * nothing is copied to the host.  tile_bytes: as zscrc_pack_opts'.
+ * Limits: n, n_tx <= 2^31 - 1, src_size <= 2^62. */
+typedef struct zscrc_log_opts { uint64_t tile_bytes; uint32_t prev_crc; } zscrc_log_opts;  /* NULL = defaults */
+#define ZSCRC_LOG_FINALISE 1u
+#define ZSCRC_LOG_RES_WORDS 8
+/* A host-computable upper bound on the end offset of a call at at == 0 (add at
+ * - 40 for an append): 40 + 54 n + 24 n_commits + sum_key_len + sum_val_len;
+ * 0 if that wraps.  n_commits counts the finalise commit.  (Exact: 40 + the sum
+ * over the records of 24 + rup8(key_len), + 16 + rup8(val_len) unless a delete,
+ * + the sum over the commits of 8, or 24 for a span above 16,777,215 bytes.) */
+uint64_t zscrc_device_log_bound(uint64_t n, uint64_t n_commits, uint64_t sum_key_len, uint64_t sum_val_len);
+/* Bytes of scratch zscrc_device_log needs for n records in n_tx transactions
+ * (one a record: n_tx = n): 12 a record, 28 a transaction, 16 per 1,024 records,
+ * 8 per 1,024 transactions and a few words; a multiple of 16, monotone in
+ * both.  0 = a bad option or a count above the limit. */
+size_t zscrc_device_log_scratch_bytes(size_t n, size_t n_tx, const zscrc_log_opts *opts);
+/* Asynchronous on `stream`.  Optional outputs, each may be NULL (the two span
+ * arrays together): d_new_recs[i] (n entries) is exactly what zscrc_zs_records
+ * lists for record i of the written bytes, offsets into the image, a delete
+ * with ZSCRC_ZS_DELETED and val_len 0; d_span_off[c] / d_span_len[c] (one per
+ * commit written, the finalise commit included) are what zscrc_zs_walk lists
+ * for commit c: the input of zscrc_device_verify_commits without a walk.
+ * d_res (device, ZSCRC_LOG_RES_WORDS words), on 0 or OVERFLOW:
+ *   [0] 0 = written; ZSCRC_ZS_OVERFLOW = the end offset exceeds out_cap: no
+ *       byte of d_out and no optional output is written (d_out == NULL with
+ *       out_cap == 0 is the sizing call)
+ *   [1] n   [2] the end offset = the new file size   [3] the bytes written
+ *       ([2] - at)   [4] the commits written -- [2] .. [4] exact for both codes
+ *       ([2], [3] UINT64_MAX if they do not fit 64 bits)
+ *   [5] how many of the commits are long   [6] the CRC of the last
+ *       transaction's span (prev_crc handed through where the call has no
+ *       transaction): what a later call passes as prev_crc   [7] the stored
+ *       CRC of the last commit record written -- [5] .. [7] 0 unless [0] == 0
+ * on bad input: [0] (uint64_t)(int64_t)ZSCRC_EINVAL; [1] the smallest index of
+ * a record that does not lie inside [0, src_size) (checked against the bytes
+ * left, never with an add that can wrap) or is a long delete, UINT64_MAX if
+ * none; [2] the smallest index of a bad table entry (below its predecessor,
+ * above n, or a last entry that is not n), UINT64_MAX if none; [3] .. [7] 0; no
+ * byte of d_out and no optional output is written.
+ * scratch: 16-byte aligned device memory of zscrc_device_log_scratch_bytes
+ * bytes, or NULL for the walk's per-device library scratch (zscrc_device_walk).
+ * ZSCRC_EINVAL before any device call: d_res NULL; uuid NULL with at == 0;
+ * n > 0 with d_recs NULL; n_tx > 0 with d_tx_end NULL; one span array without
+ * the other; d_src NULL with src_size > 0; out_cap > 0 with d_out NULL; d_out or
+ * scratch not 16-byte aligned; at neither 0 nor a multiple of 8 from 40 up;
+ * at > out_cap with out_cap > 0; an unknown flag; a bad option; n, n_tx or
+ * src_size above its limit; [d_out + at, d_out + out_cap) overlapping [d_src,
+ * + src_size). */
+int zscrc_device_log(const void *d_src, uint64_t src_size,
+                     const struct zscrc_zs_record *d_recs, size_t n,
+                     const uint64_t *d_tx_end, size_t n_tx,
+                     const uint8_t uuid[16], uint32_t startidx, uint32_t endidx,
+                     void *d_out, uint64_t out_cap, uint64_t at,
+                     struct zscrc_zs_record *d_new_recs,
+                     uint64_t *d_span_off, uint64_t *d_span_len,
+                     uint64_t *d_res, void *scratch,
+                     const zscrc_log_opts *opts, unsigned flags, void *stream);
+/* The same for a list, a table and bytes in host memory, on one core: the same
+ * image, result words (res: a host array) and optional outputs, by the same
+ * layout functions and the host CRC.  out needs no alignment; tile_bytes is
+ * checked and otherwise unused.  Returns ZSCRC_EINVAL on the arguments
+ * zscrc_device_log refuses (alignment aside), ZSCRC_ENOMEM, else ZSCRC_OK with
+ * the verdict in res[0]. */
+int zscrc_zs_log(const void *src, uint64_t src_size,
+                 const struct zscrc_zs_record *recs, size_t n,
+                 const uint64_t *tx_end, size_t n_tx,
+                 const uint8_t uuid[16], uint32_t startidx, uint32_t endidx,
+                 void *out, uint64_t out_cap, uint64_t at,
+                 struct zscrc_zs_record *new_recs,
+                 uint64_t *span_off, uint64_t *span_len,
+                 uint64_t res[ZSCRC_LOG_RES_WORDS],
+                 const zscrc_log_opts *opts, unsigned flags);
+
 /* The key merge on the device: the sort by key and the winner loop of
  * zscrc_zs_repack for record lists that live in device memory -- the step
  * between zscrc_device_records and zscrc_device_pack, without a key crossing

@@ -112,6 +112,12 @@ SIGNATURES = {
     "zscrc_device_pack_scratch_bytes": (_sz, [_sz, _vp]),
     "zscrc_device_pack": (_int, [_vp, _u64, _vp, _sz, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, ctypes.c_uint,
                                  _vp]),
+    "zscrc_device_log_bound": (_u64, [_u64, _u64, _u64, _u64]),
+    "zscrc_device_log_scratch_bytes": (_sz, [_sz, _sz, _vp]),
+    "zscrc_device_log": (_int, [_vp, _u64, _vp, _sz, _vp, _sz, _vp, _u32, _u32, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp,
+                                _vp, ctypes.c_uint, _vp]),
+    "zscrc_zs_log": (_int, [_vp, _u64, _vp, _sz, _vp, _sz, _vp, _u32, _u32, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _vp,
+                            ctypes.c_uint]),
     "zscrc_device_merge_scratch_bytes": (_sz, [_sz, _vp]),
     "zscrc_device_merge": (_int, [_vp, _u64, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.c_uint, _vp]),
     "zscrc_device_find_scratch_bytes": (_sz, [_sz, _vp]),

@@ -41,7 +41,7 @@ inline bool same_stream(hipStream_t a, hipStream_t b)
 
 /* The library-owned scratch of the device stages (zscrc_scratch.cpp), one
  * buffer per device, shared by every call there that passes no scratch of its
- * own (zscrc_device_walk, _records, _walk_multi, _pack, _merge): a call on
+ * own (zscrc_device_walk, _records, _walk_multi, _pack, _merge, _log): a call on
  * another stream than the last user's waits for that user's work. */
 struct Scratch {
     std::mutex mu;
@@ -480,14 +480,14 @@ struct SpanFolds {
 } /* namespace zs */
 
 /* What the device stages (zscrc_walk.hip, zscrc_devpack.hip, zscrc_merge.hip,
- * zscrc_find.hip, zscrc_gather.hip, zscrc_scan.hip) share on host and device;
+ * zscrc_find.hip, zscrc_gather.hip, zscrc_scan.hip, zscrc_devlog.hip) share on host and device;
  * their workgroup primitives: zscrc_wg.h, the scratch layout of a call:
  * zs::Carve (zscrc_carve.h), the staged list descriptors: zscrc_lists.h. */
 namespace zsdev {
 
 constexpr int WG = 256;
-/* the packer, the merge, the gather and the scan cut a list into blocks, one
- * workgroup each */
+/* the packer, the merge, the gather, the scan and the log writer cut a list into
+ * blocks, one workgroup each */
 constexpr uint32_t PER = 4;                  /* records a thread of a block */
 constexpr uint32_t BLOCK_RECS = WG * PER;
 constexpr uint64_t N_MAX = (1ull << 31) - 1; /* records of one call */

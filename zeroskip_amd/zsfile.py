@@ -179,6 +179,141 @@ def device_records(d_image: torch.Tensor, kind: int = ACTIVE, cap: int | None = 
     return recs, res
 
 
+class LogOpts(ctypes.Structure):
+    """zscrc_log_opts (include/zscrc.h); 0 = the default."""
+    _fields_ = [("tile_bytes", ctypes.c_uint64), ("prev_crc", ctypes.c_uint32)]
+
+
+LOG_FINALISE = 1  # ZSCRC_LOG_FINALISE
+LOG_RES_WORDS = 8  # ZSCRC_LOG_RES_WORDS
+_LOG_NAMES = ("code", "n", "end", "written", "commits", "long_commits", "last_crc", "stored_crc")
+
+
+def device_log_bound(n: int, n_commits: int, sum_key_len: int, sum_val_len: int) -> int:
+    """An upper bound on the end offset of a log written from its header
+    (zscrc_device_log_bound): 40 + 54 n + 24 n_commits + the sums; 0 if it wraps."""
+    return lib().zscrc_device_log_bound(n, n_commits, sum_key_len, sum_val_len)
+
+
+def device_log_scratch_bytes(n: int, n_tx: int, tile_bytes: int = 0) -> int:
+    """zscrc_device_log_scratch_bytes (one transaction a record: n_tx = n); 0 = a
+    bad option or a count above the limit."""
+    return lib().zscrc_device_log_scratch_bytes(n, n_tx, ctypes.byref(LogOpts(tile_bytes, 0)))
+
+
+def _log_result(res, image, new_recs, span_off, span_len) -> dict:
+    """The result words by name (res: uint64 host words) around the outputs."""
+    d = {k: int(v) for k, v in zip(_LOG_NAMES, res)}
+    d["code"] = int(np.int64(res[0]))
+    if d["code"] == -1:  # bad input: [1] the first bad record, [2] the first bad table entry, or -1
+        d["bad_record"], d["bad_tx"] = int(np.int64(res[1])), int(np.int64(res[2]))
+        d["n"] = d["end"] = 0
+    ok = d["code"] == 0
+    nc = d["commits"] if ok else 0
+    d["image"] = image[:d["end"]] if ok and image is not None else None
+    d["new_recs"] = new_recs if ok else None
+    d["span_off"] = span_off[:nc] if ok and span_off is not None else None
+    d["span_len"] = span_len[:nc] if ok and span_len is not None else None
+    return d
+
+
+def device_log(d_src: torch.Tensor, recs: torch.Tensor, tx_end: torch.Tensor | None = None, uuid: bytes = bytes(16),
+               startidx: int = 0, endidx: int = 0, out: torch.Tensor | None = None, at: int = 0, finalise: bool = False,
+               prev_crc: int = 0, tile_bytes: int = 0, new_recs: bool = False, spans: bool = False,
+               scratch: torch.Tensor | None = None) -> dict:
+    """A batch of puts and deletes appended to an active log image on the GPU
+    (zscrc_device_log): what zsdb_add / zsdb_remove / zsdb_commit write, commit
+    CRCs included.  d_src: the uint8 device tensor the records' offsets point
+    into; recs: int64 [n, 4] device tensor (key_off, key_len, val_off or DELETED,
+    val_len); tx_end: int64 device tensor of exclusive transaction ends
+    (non-decreasing, the last one n; an empty tensor = no transaction), None =
+    one transaction a record.  at = 0: a new image, header from uuid, startidx,
+    endidx; at >= 40 (a multiple of 8): appended at that offset of `out`.
+    finalise: the stale-register finalise commit behind the last transaction
+    (hashed from prev_crc where the call has no transaction).  out: a 16-byte
+    aligned uint8 device tensor, the image's base; None: one of at +
+    device_log_bound() bytes from the torch sums of the lengths (one more
+    read-back).  Returns a dict: image (out cut to the end offset; None unless
+    code == 0), res (the int64 device words) and its words by name -- code (0
+    written, 3 does not fit out, -1 bad input: then bad_record / bad_tx, -1 =
+    none), n, end, written, commits, long_commits, last_crc (what a later call
+    passes as prev_crc), stored_crc -- read back once, as device_pack reads its
+    size; new_recs ([n, 4], what device_records lists for the written bytes) and
+    span_off / span_len (one per commit: verify_commits' input) when asked for.
+    scratch: a 16-byte aligned uint8 tensor of device_log_scratch_bytes() bytes
+    (default: the library's own, stream-ordered)."""
+    dev = d_src.device
+    n = int(recs.shape[0])
+    assert recs.dtype == torch.int64 and recs.is_contiguous() and (n == 0 or recs.shape[1] == 4)
+    assert at != 0 or len(uuid) == 16
+    n_tx = 0 if tx_end is None else int(tx_end.numel())
+    assert tx_end is None or (tx_end.dtype == torch.int64 and tx_end.is_contiguous())
+    nc = (n if tx_end is None else n_tx) + (1 if finalise else 0)
+    if out is None:
+        # a delete's val_len is ignored by the writer
+        vlen = torch.where(recs[:, 2] == DELETED, 0, recs[:, 3]) if n else None
+        sums = torch.stack((recs[:, 1].sum(), vlen.sum())).cpu() if n else (0, 0)
+        bound = device_log_bound(n, nc, int(sums[0]) & (2**64 - 1), int(sums[1]) & (2**64 - 1))
+        assert bound, "the size bound wraps"
+        out = torch.empty(bound + (at - 40 if at else 0), dtype=torch.uint8, device=dev)
+    cap = out.numel() * out.element_size()
+    res = torch.empty(LOG_RES_WORDS, dtype=torch.int64, device=dev)
+    nr = torch.empty((max(n, 1), 4), dtype=torch.int64, device=dev) if new_recs else None
+    so = torch.empty(max(nc, 1), dtype=torch.int64, device=dev) if spans else None
+    sl = torch.empty(max(nc, 1), dtype=torch.int64, device=dev) if spans else None
+    src_bytes = d_src.numel() * d_src.element_size()
+    opts = LogOpts(tile_bytes, prev_crc)
+    with torch.cuda.device(dev):
+        check(lib().zscrc_device_log(
+            d_src.data_ptr() if src_bytes else None, src_bytes, recs.data_ptr() if n else None, n,
+            None if tx_end is None else (tx_end.data_ptr() if n_tx else res.data_ptr()), n_tx,
+            bytes(uuid), startidx, endidx, out.data_ptr() if cap else None, cap, at,
+            None if nr is None else nr.data_ptr(), None if so is None else so.data_ptr(),
+            None if sl is None else sl.data_ptr(), res.data_ptr(),
+            None if scratch is None else scratch.data_ptr(), ctypes.byref(opts), LOG_FINALISE if finalise else 0,
+            torch.cuda.current_stream(dev).cuda_stream), "zscrc_device_log")
+    d = _log_result(res.cpu().numpy().view(np.uint64), out, None if nr is None else nr[:n], so, sl)
+    d["res"] = res
+    return d
+
+
+def log(src, recs, tx_end=None, uuid: bytes = bytes(16), startidx: int = 0, endidx: int = 0, out=None, at: int = 0,
+        finalise: bool = False, prev_crc: int = 0, tile_bytes: int = 0, new_recs: bool = False,
+        spans: bool = False) -> dict:
+    """device_log in host memory (zscrc_zs_log, one thread, no device): the same
+    image, words and optional outputs as numpy arrays for the same bytes.  src:
+    bytes or a uint8 array; recs [n, 4] uint64 or int64; tx_end: a sequence of
+    exclusive ends or None; out: a writable uint8 array (the image's base) or
+    None for one of at + device_log_bound() bytes."""
+    s, sp, sn = _host(src)
+    r = np.ascontiguousarray(recs).view(np.uint64).reshape(-1, 4)
+    n = len(r)
+    te = None if tx_end is None else np.ascontiguousarray(tx_end, dtype=np.uint64).reshape(-1)
+    n_tx = 0 if te is None else len(te)
+    nc = (n if te is None else n_tx) + (1 if finalise else 0)
+    if out is None:
+        with np.errstate(over="ignore"):
+            vlen = np.where(r[:, 2] == np.uint64(2**64 - 1), np.uint64(0), r[:, 3])  # a delete's is ignored
+            bound = device_log_bound(n, nc, int(r[:, 1].sum(dtype=np.uint64)), int(vlen.sum(dtype=np.uint64)))
+        assert bound, "the size bound wraps"
+        out = np.zeros(bound + (at - 40 if at else 0), np.uint8)
+    assert out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable
+    res = np.zeros(LOG_RES_WORDS, np.uint64)
+    nr = np.zeros((max(n, 1), 4), np.uint64) if new_recs else None
+    so = np.zeros(max(nc, 1), np.uint64) if spans else None
+    sl = np.zeros(max(nc, 1), np.uint64) if spans else None
+    opts = LogOpts(tile_bytes, prev_crc)
+    check(lib().zscrc_zs_log(sp if sn else None, sn, r.ctypes.data if n else None, n,
+                             None if te is None else (te.ctypes.data if n_tx else res.ctypes.data), n_tx,
+                             bytes(uuid), startidx, endidx, out.ctypes.data if out.nbytes else None, out.nbytes, at,
+                             None if nr is None else nr.ctypes.data, None if so is None else so.ctypes.data,
+                             None if sl is None else sl.ctypes.data, res.ctypes.data, ctypes.byref(opts),
+                             LOG_FINALISE if finalise else 0), "zscrc_zs_log")
+    d = _log_result(res, out, None if nr is None else nr[:n], so, sl)
+    d["res"] = res
+    return d
+
+
 class WalkImage(ctypes.Structure):
     """zscrc_walk_image (include/zscrc.h): bytes [off, off + size) of an arena."""
     _fields_ = [("off", ctypes.c_uint64), ("size", ctypes.c_uint64)]
