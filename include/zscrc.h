@@ -1196,6 +1196,113 @@ int zscrc_zs_scan(const void *src, uint64_t src_size, const zscrc_merge_list *le
                   struct zscrc_zs_record *out, size_t cap, uint64_t *offs, uint64_t *seq,
                   uint64_t res[ZSCRC_SCAN_RES_WORDS], unsigned flags);
 
+/* The successor on the device: for every key of a batch, the next `page` live
+ * keys after it across k sorted lists that live in device memory, in key order,
+ * each key once from the newest list that holds it -- the successor of a key
+ * (page = 1), or one page of an iteration that starts anywhere and goes on from
+ * where it stopped without a byte leaving the device.  (The reference's
+ * zsdb_fetchnext, src/zeroskip.c:1175-1254, returns the smallest key after a
+ * given key over all files, newest record first.)
+ * Levels, base, the sequence number seq = n_0 + .. + n_(l-1) + j, the query
+ * list and the bad-query rule mean exactly what they mean in
+ * zscrc_device_find: `levels` is a HOST array of k <= ZSCRC_FIND_LEVELS_MAX
+ * lists over the one d_src, staged through the pinned staging, level 0 has
+ * priority, each level's keys ascend strictly in memcmp_raw order; query i is
+ * the key d_qsrc[key_off, +key_len) of d_queries[i], the value words are never
+ * read, and a key that does not lie inside [0, qsrc_size) is a bad query.
+ * The step: query i has one cursor per level that is not empty, the index of
+ * the level's first key greater than the query's key -- with
+ * ZSCRC_NEXT_INCLUSIVE the first key not smaller.  Before every step, in this
+ * order: count == page ends the query in state PAGE; no cursor with a record
+ * left, in state END; max_steps != 0 and that many steps taken, in state MORE.
+ * A step takes the smallest key under the cursors; every level whose cursor
+ * holds that key advances by one; the record of the lowest such level wins and
+ * the others are counted as superseded.  A winner that is a delete is counted,
+ * and becomes a row only with ZSCRC_NEXT_KEEP_DELETES; any other winner becomes
+ * a row.  This is deliberately not zsdb_fetchnext's behaviour, which hands out
+ * whatever record its iterator stands on, a delete included: deletes are
+ * dropped or flagged the way zscrc_device_scan does it.  max_steps bounds the
+ * work of a query that runs into a long stretch of deleted keys; MORE says so
+ * and the cursor goes on from there.
+ * Outputs, all written in full on every call whose code is not EINVAL: d_out
+ * (nq * page entries): the slots [i * page, i * page + count_i) hold query i's
+ * rows in key order, a row being the winning record's four words rebased as
+ * zscrc_device_scan writes them; the slots after them hold {ZSCRC_FIND_NONE, 0,
+ * 0, 0}, so the whole buffer is a gather list for zscrc_device_gather as it
+ * stands, the filler slots counting as "not found".  d_seq (NULL, or nq * page
+ * words): the winner's seq, UINT64_MAX in a filler slot.  d_cur (nq entries):
+ * count and state, and for PAGE and MORE in key_off and key_len the last key a
+ * step took inside d_src, whether it became a row or a dropped delete: d_cur is
+ * the query list of the next call with d_qsrc = d_src and without INCLUSIVE
+ * (its last two words lie where a query's value words do).  For END and BAD the
+ * key is {ZSCRC_FIND_NONE, 0}: such a cursor fed again is a bad query, so a
+ * chain of calls is over when every state is END or BAD.
+ * d_res (device, ZSCRC_NEXT_RES_WORDS words):
+ *   [0] 0; (uint64_t)(int64_t)ZSCRC_EINVAL = a level record outside the source
+ *       or, with ZSCRC_NEXT_CHECK_ORDER, an order offence, both decided as in
+ *       zscrc_device_find: nothing of d_out, d_seq or d_cur is written
+ *   [1] nq; on EINVAL the smallest offending seq, bounds offences before order
+ *       offences
+ *   [2] the rows   [3] the steps   [4] superseded copies passed
+ *   [5] winning deletes met   [6] bad queries
+ *   [7] on EINVAL 1 for an order offence
+ *   [8] the sum of key_len over the rows   [9] the sum of val_len over the rows
+ *       that are not deletes
+ *   [10] queries that ended END   [11] queries that ended MORE
+ * Without KEEP_DELETES [3] == [2] + [5]; with it [3] == [2].  The queries that
+ * ended PAGE number nq - [6] - [10] - [11].  Counts are integer atomics and
+ * workgroup sums only: two runs are bit for bit equal, and nothing depends on
+ * `splitters` (zscrc_find_opts' meaning).  Every level record is bounds-checked
+ * on every call.  Without CHECK_ORDER a level that does not ascend is stepped
+ * through all the same: every step advances a cursor, so a query takes at most
+ * n_total steps and every store stays inside d_out, d_seq, d_cur and the
+ * scratch; the rows are then unspecified.
+ * Launches in stream order (the lookup's check and splitter tables; one bounds
+ * launch per level that is not empty on a persistent grid, the level's table in
+ * LDS, each query's cursor into a level-major matrix; the step launch, one
+ * thread a query; one lane that seals); every grid is sized on the host from
+ * n_total, k, nq and page, no workgroup waits for another, nothing is copied to
+ * the host.
+ * Limits: find's; 1 <= page <= 65536; nq * page <= 2^31 - 1.
+ * scratch: 16-byte aligned device memory of zscrc_device_next_scratch_bytes
+ * bytes, or NULL for the per-device library scratch.  With up16(x) = x rounded
+ * up to 16 the size is
+ *   128 + up16(32 (k + 1)) + (splitters > 1 ? 32 splitters k : 0)
+ *   + up16(4 nq k):
+ * the lookup's head and 4 bytes a (query, level) cursor.  A multiple of 16,
+ * monotone in each argument; 0 = a bad option or an argument above its limit.
+ * ZSCRC_EINVAL before any device call: on zscrc_device_find's conditions (d_res
+ * NULL; nq > 0 with d_queries NULL; k > 0 with levels NULL; k > 64; a level
+ * with n > 0 and d_recs NULL; d_src NULL with src_size > 0, and likewise
+ * d_qsrc; src_size or qsrc_size > 2^62; n_total or nq > 2^31 - 1; scratch not
+ * 16-byte aligned; a bad option), and: page 0 or above 65536; nq * page above
+ * 2^31 - 1; nq > 0 with d_out or d_cur NULL; an unknown flag. */
+typedef struct zscrc_next_opts { uint32_t splitters; uint32_t max_steps; } zscrc_next_opts;   /* NULL / 0 = default */
+typedef struct zscrc_next_cursor { uint64_t key_off, key_len, count, state; } zscrc_next_cursor;
+#define ZSCRC_NEXT_PAGE 0u   /* `page` rows written; more may follow        */
+#define ZSCRC_NEXT_END  1u   /* every level ran out before the page filled  */
+#define ZSCRC_NEXT_MORE 2u   /* max_steps steps taken before either         */
+#define ZSCRC_NEXT_BAD  3u   /* the query's key does not lie inside d_qsrc  */
+#define ZSCRC_NEXT_INCLUSIVE    1u
+#define ZSCRC_NEXT_CHECK_ORDER  2u
+#define ZSCRC_NEXT_KEEP_DELETES 4u
+#define ZSCRC_NEXT_RES_WORDS    12
+size_t zscrc_device_next_scratch_bytes(size_t nq, size_t k, const zscrc_next_opts *opts);
+int zscrc_device_next(const void *d_src, uint64_t src_size,
+                      const zscrc_merge_list *levels, size_t k,
+                      const void *d_qsrc, uint64_t qsrc_size,
+                      const struct zscrc_zs_record *d_queries, size_t nq,
+                      uint32_t page, struct zscrc_zs_record *d_out, uint64_t *d_seq, zscrc_next_cursor *d_cur,
+                      uint64_t *d_res, void *scratch, const zscrc_next_opts *opts, unsigned flags, void *stream);
+/* The same for lists and keys in host memory, one thread, no device: the same
+ * words for the same bytes, each query run through the same inline loop as the
+ * kernel's (zscrc_next_order.h).  max_steps is zscrc_next_opts'.  The argument
+ * checks are zscrc_device_next's without scratch and options. */
+int zscrc_zs_next(const void *src, uint64_t src_size, const zscrc_merge_list *levels, size_t k,
+                  const void *qsrc, uint64_t qsrc_size, const struct zscrc_zs_record *queries, size_t nq,
+                  uint32_t page, struct zscrc_zs_record *out, uint64_t *seq, zscrc_next_cursor *cur,
+                  uint64_t res[ZSCRC_NEXT_RES_WORDS], uint32_t max_steps, unsigned flags);
+
 /* `consistent` for one process / one GPU (zsdb_consistent,
  * src/zeroskip.c:1399-1407, and tool/cmd-consistent.c:23-49 are stubs in the
  * reference): every .zsdb / header / commit CRC of the DB directory,

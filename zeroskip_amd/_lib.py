@@ -130,6 +130,10 @@ SIGNATURES = {
     "zscrc_device_scan": (_int, [_vp, _u64, _vp, _sz, _vp, _u64, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp,
                                  ctypes.c_uint, _vp]),
     "zscrc_zs_scan": (_int, [_vp, _u64, _vp, _sz, _vp, _u64, _vp, _sz, _vp, _sz, _vp, _vp, _vp, ctypes.c_uint]),
+    "zscrc_device_next_scratch_bytes": (_sz, [_sz, _sz, _vp]),
+    "zscrc_device_next": (_int, [_vp, _u64, _vp, _sz, _vp, _u64, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 ctypes.c_uint, _vp]),
+    "zscrc_zs_next": (_int, [_vp, _u64, _vp, _sz, _vp, _u64, _vp, _sz, _u32, _vp, _vp, _vp, _vp, _u32, ctypes.c_uint]),
 }
 ABI_VERSION = 4  # include/zscrc.h ZSCRC_ABI_VERSION
 

@@ -1,12 +1,13 @@
 /*
- * zscrc_find_levels.h -- what the device lookup (zscrc_find.hip) and the
- * device prefix scan (zscrc_scan.hip) share: the levels of a call (descriptors
- * as zscrc_lists.h stages them), the check of every level record and the
- * splitter tables, the levels' part of the scratch, the walk over the levels
- * that are not empty, and the host code that launches the check and the tables
- * and checks the arguments both entry points take.  The host functions are
- * defined once, in zscrc_find.hip, with the two kernels they launch; this
- * header declares them and holds the inline pieces either file calls.
+ * zscrc_find_levels.h -- what the device lookup (zscrc_find.hip), the device
+ * prefix scan (zscrc_scan.hip) and the successor stage (zscrc_next.hip) share:
+ * the levels of a call (descriptors as zscrc_lists.h stages them), the check of
+ * every level record and the splitter tables, the levels' part of the scratch,
+ * the walk over the levels that are not empty, and the host code that launches
+ * the check and the tables and checks the arguments their entry points take.
+ * The host functions are defined once, in zscrc_find.hip, with the two kernels
+ * they launch; this header declares them and holds the inline pieces each file
+ * calls.
  */
 #ifndef ZSCRC_FIND_LEVELS_H
 #define ZSCRC_FIND_LEVELS_H

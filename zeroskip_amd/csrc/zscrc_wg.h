@@ -1,7 +1,7 @@
 /*
  * zscrc_wg.h -- the workgroup primitives of the device stages (zscrc_walk.hip,
  * zscrc_devpack.hip, zscrc_merge.hip, zscrc_find.hip, zscrc_gather.hip,
- * zscrc_scan.hip, zscrc_devlog.hip): a sum, an exclusive prefix sum and the one-workgroup scan of
+ * zscrc_scan.hip, zscrc_next.hip, zscrc_devlog.hip): a sum, an exclusive prefix sum and the one-workgroup scan of
  * a long array of counts, and the 16-byte word of the tiled copies.  Device
  * code only, for workgroups of WG = 256 threads in waves of 64.
  *

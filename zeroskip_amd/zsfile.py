@@ -798,6 +798,138 @@ def device_foreach(d_src: torch.Tensor, levels, d_qsrc: torch.Tensor, queries: t
     return rows, offs, values, voffs, crc, sres, gres
 
 
+class NextOpts(ctypes.Structure):
+    """zscrc_next_opts (include/zscrc.h); 0 = the default."""
+    _fields_ = [("splitters", ctypes.c_uint32), ("max_steps", ctypes.c_uint32)]
+
+
+NEXT_PAGE = 0  # ZSCRC_NEXT_PAGE
+NEXT_END = 1  # ZSCRC_NEXT_END
+NEXT_MORE = 2  # ZSCRC_NEXT_MORE
+NEXT_BAD = 3  # ZSCRC_NEXT_BAD
+NEXT_INCLUSIVE = 1  # ZSCRC_NEXT_INCLUSIVE
+NEXT_CHECK_ORDER = 2  # ZSCRC_NEXT_CHECK_ORDER
+NEXT_KEEP_DELETES = 4  # ZSCRC_NEXT_KEEP_DELETES
+NEXT_RES_WORDS = 12  # ZSCRC_NEXT_RES_WORDS
+NEXT_PAGE_MAX = 65536  # zscrc_next_order.h PAGE_MAX
+
+
+def _next_flags(inclusive: bool, keep_deletes: bool, check_order: bool) -> int:
+    return (NEXT_INCLUSIVE if inclusive else 0) | (NEXT_KEEP_DELETES if keep_deletes else 0) | \
+        (NEXT_CHECK_ORDER if check_order else 0)
+
+
+def device_next_scratch_bytes(nq: int, k: int, splitters: int = 0) -> int:
+    """zscrc_device_next_scratch_bytes; 0 = a bad option or an argument above its limit."""
+    return lib().zscrc_device_next_scratch_bytes(nq, k, ctypes.byref(NextOpts(splitters, 0)))
+
+
+def device_next(d_src: torch.Tensor, levels, d_qsrc: torch.Tensor, queries: torch.Tensor, page: int = 1,
+                inclusive: bool = False, keep_deletes: bool = False, check_order: bool = False, max_steps: int = 0,
+                splitters: int = 0, out: tuple | None = None, scratch: torch.Tensor | None = None):
+    """The next `page` live keys after every key of a batch in device-resident
+    sorted record lists on the GPU (zscrc_device_next), asynchronous on the
+    current stream and never reading anything back: (rows [nq, page, 4], seq
+    [nq, page], cur [nq, 4], res [12]) int64 device tensors.  d_src, levels,
+    d_qsrc and queries are device_find's.  rows[i, :count_i]: the records of
+    the keys greater than query i's (inclusive: not smaller), in key order,
+    each key once from the first level that holds it, rebased as device_scan
+    writes them; a key whose winning record is a delete is left out unless
+    keep_deletes.  The slots after them hold [FIND_NONE, 0, 0, 0] and seq -1,
+    so rows.view(-1, 4) is a gather list as it stands.  cur[i]: [key_off,
+    key_len, count, state]; state NEXT_PAGE (the page is full), NEXT_END (the
+    levels ran out), NEXT_MORE (max_steps steps taken, 0 = no limit) or
+    NEXT_BAD (the query's key lies outside d_qsrc).  For PAGE and MORE the
+    key is the last one a step took, inside d_src: cur is the query list of
+    the next call with d_qsrc = d_src and inclusive=False; for END and BAD it
+    is [FIND_NONE, 0], a bad query.  res: [code (0; -1 = a level record
+    outside d_src or, with check_order, a key not above its predecessor's:
+    nothing written), nq or the first offending sequence number, rows, steps,
+    superseded, winning deletes, bad queries, 1 = an order offence, sum of the
+    rows' key lengths, sum of their value lengths, queries ended END, queries
+    ended MORE].  splitters: device_find's; the result never depends on it.
+    out: preallocated (rows, seq | None, cur, res); scratch: a 16-byte aligned
+    uint8 tensor of device_next_scratch_bytes(nq, k) bytes (default: the
+    library's own, stream-ordered)."""
+    dev = d_src.device
+    arr, k = _find_levels(levels, lambda r: r.data_ptr())
+    for recs, _ in levels:
+        assert recs.dtype == torch.int64 and recs.is_contiguous()
+    nq = int(queries.shape[0])
+    assert queries.dtype == torch.int64 and queries.is_contiguous() and (nq == 0 or queries.shape[1] == 4)
+    if out is None:
+        out = (torch.empty((nq, page, 4), dtype=torch.int64, device=dev),
+               torch.empty((nq, page), dtype=torch.int64, device=dev),
+               torch.empty((nq, 4), dtype=torch.int64, device=dev),
+               torch.empty(NEXT_RES_WORDS, dtype=torch.int64, device=dev))
+    rows, seq, cur, res = out
+    assert rows.numel() >= 4 * nq * page and (seq is None or seq.numel() >= nq * page) and cur.numel() >= 4 * nq and \
+        res.numel() >= NEXT_RES_WORDS
+    src_bytes = d_src.numel() * d_src.element_size()
+    q_bytes = d_qsrc.numel() * d_qsrc.element_size()
+    opts = NextOpts(splitters, max_steps)
+    with torch.cuda.device(dev):
+        check(lib().zscrc_device_next(
+            d_src.data_ptr() if src_bytes else None, src_bytes, arr, k, d_qsrc.data_ptr() if q_bytes else None,
+            q_bytes, queries.data_ptr() if nq else None, nq, page, rows.data_ptr() if nq else None,
+            seq.data_ptr() if seq is not None and nq else None, cur.data_ptr() if nq else None, res.data_ptr(),
+            None if scratch is None else scratch.data_ptr(), ctypes.byref(opts),
+            _next_flags(inclusive, keep_deletes, check_order), torch.cuda.current_stream(dev).cuda_stream),
+            "zscrc_device_next")
+    return rows, seq, cur, res
+
+
+def next_(src, levels, qsrc, queries, page: int = 1, inclusive: bool = False, keep_deletes: bool = False,
+          check_order: bool = False, max_steps: int = 0):
+    """device_next for lists and keys in host memory (zscrc_zs_next, one
+    thread, no device): (rows int64 [nq, page, 4], seq int64 [nq, page], cur
+    int64 [nq, 4], res int64 [12]) numpy arrays, the same words for the same
+    bytes.  src, qsrc: bytes or uint8 arrays; levels: (recs, base) with recs
+    [n, 4] uint64 or int64 arrays; queries [nq, 4] (a cur of an earlier call
+    among them).  The underscore: next is a builtin."""
+    s, sp, sn = _host(src)
+    q, qp, qn = _host(qsrc)
+    levels = [(np.ascontiguousarray(r).view(np.int64).reshape(-1, 4), b) for r, b in levels]
+    arr, k = _find_levels(levels, lambda r: r.ctypes.data)
+    qr = np.ascontiguousarray(queries).view(np.int64).reshape(-1, 4)
+    nq = len(qr)
+    rows, seq = np.empty((nq, page, 4), np.int64), np.empty((nq, page), np.int64)
+    cur = np.empty((nq, 4), np.int64)
+    res = np.empty(NEXT_RES_WORDS, np.int64)
+    check(lib().zscrc_zs_next(sp if sn else None, sn, arr, k, qp if qn else None, qn, qr.ctypes.data if nq else None,
+                              nq, page, rows.ctypes.data if nq else None, seq.ctypes.data if nq else None,
+                              cur.ctypes.data if nq else None, res.ctypes.data, max_steps,
+                              _next_flags(inclusive, keep_deletes, check_order)), "zscrc_zs_next")
+    return rows, seq, cur, res
+
+
+def device_fetchnext(d_src: torch.Tensor, levels, d_qsrc: torch.Tensor, queries: torch.Tensor, page: int = 1,
+                     inclusive: bool = False, keep_deletes: bool = False, check_order: bool = False,
+                     max_steps: int = 0, splitters: int = 0, tile_bytes: int = 0):
+    """The next keys with their values on the GPU: device_next, then
+    device_gather over its rows for the values and a second gather for the
+    keys, in one call: (keys, key_offs, values, value_offs, rows, seq, cur,
+    next_res, gather_res).  Slot r = i * page + j is row j of query i: its key
+    is keys[key_offs[r]:key_offs[r + 1]], its value values[value_offs[r]:
+    value_offs[r + 1]]; a filler slot has neither, a kept delete a key only.
+    The key gather reads a view of the rows built with torch, the key words
+    in the value words.  It is to device_next what device_foreach is to
+    device_scan: the gathers size themselves from their result words.  A
+    next that refuses its levels (next_res[0] = -1) writes no row; the gathers
+    are then not run and keys, key_offs, values, value_offs and gather_res
+    are None."""
+    rows, seq, cur, nres = device_next(d_src, levels, d_qsrc, queries, page=page, inclusive=inclusive,
+                                       keep_deletes=keep_deletes, check_order=check_order, max_steps=max_steps,
+                                       splitters=splitters)
+    if int(nres[0].cpu()) != 0:
+        return None, None, None, None, rows, seq, cur, nres, None
+    items = rows.view(-1, 4)
+    values, voffs, _, gres = device_gather(d_src, items, tile_bytes=tile_bytes)
+    as_values = torch.stack((items[:, 0], torch.zeros_like(items[:, 0]), items[:, 0], items[:, 1]), dim=1).contiguous()
+    keys, koffs, _, _ = device_gather(d_src, as_values, tile_bytes=tile_bytes)
+    return keys, koffs, values, voffs, rows, seq, cur, nres, gres
+
+
 def verify_device_images(d_arena: torch.Tensor, images) -> list:
     """verify_device_image() for the k active or finalised images [(off,
     size)] of a device-resident arena in one call (zscrc_device_verify_images):
