@@ -10,41 +10,22 @@
  *
  * and rebuilds the image the way the kernels do: lengths and delete marks to
  * P[] and D[], the table checked, the spans and C[], the totals, the starts,
- * then for each tile size the records tile by tile in file coordinates and
- * word by word (find_rec, word_in_rec, piece_at, gather8), the commit records
- * from the span CRCs, the finalise commit, the header.  The source lies at an
- * address = shift mod 8 in an allocation that ends with its last 8-byte
- * granule, so a sanitizer sees any read outside the aligned words that hold
- * source bytes.  Exit status 0 = every byte equal at every tile size.
+ * then for each tile size the records by the kernel's own tile sweep
+ * (copy_tiles_sweep.h) at four grid sizes, the commit records from the span
+ * CRCs, the finalise commit, the header.  The source lies at an address =
+ * shift mod 8 in an allocation that ends with its last 8-byte granule, so a
+ * sanitizer sees any read outside the aligned words that hold source bytes.
+ * Exit status 0 = every byte equal at every tile and grid size; the ok line
+ * counts the stores of each kind.
  */
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <vector>
 
-#include "../../zeroskip_amd/csrc/zscrc_log_layout.h"
+static const char *PROGRAM = "log_layout";
+#include "copy_tiles_sweep.h"
 
 using namespace zspack;
 using namespace zslog;
-
-static int fail(const char *what, uint64_t a, uint64_t b, uint64_t c)
-{
-    fprintf(stderr, "log_layout: %s (%llu, %llu, %llu)\n", what, (unsigned long long)a, (unsigned long long)b,
-            (unsigned long long)c);
-    return 1;
-}
-
-static uint32_t g_tab[256];
-static uint32_t crc_span(const uint8_t *p, uint64_t n)
-{
-    if (!g_tab[1])
-        for (uint32_t b = 0; b < 256; ++b)
-            g_tab[b] = ~crc_bytes(~0u, b, 1); /* the register step of one byte from 0 */
-    uint32_t c = ~0u;
-    for (uint64_t i = 0; i < n; ++i)
-        c = g_tab[(c ^ p[i]) & 0xFF] ^ (c >> 8);
-    return ~c;
-}
 
 int main(int argc, char **argv)
 {
@@ -117,40 +98,13 @@ int main(int argc, char **argv)
     start[n] = tot.body_end;
 
     const uint64_t tiles[4] = {64, 128, 4096, 65536};
+    Stores stores{0, 0, 0};
     for (uint64_t T : tiles) {
         /* 8-byte words, so that the output is built the way the kernel stores it */
-        std::vector<uint64_t> out(file_len / 8 + 1, 0xA5A5A5A5A5A5A5A5ull);
+        std::vector<uint64_t> out(file_len / 8 + 1, CANARY);
         memcpy(out.data(), want.data(), at);
-        uint64_t written = 0;
-        if (n) {
-            const uint64_t stop = tot.body_end, tlo = base / T, thi = (stop + T - 1) / T;
-            uint64_t rec0 = find_rec(start, n, base);
-            for (uint64_t t = tlo; t < thi; ++t) {
-                const uint64_t f0 = t * T, lo = f0 > base ? f0 : base, hi = f0 + T < stop ? f0 + T : stop;
-                if (lo >= hi)
-                    return fail("tile range", t, lo, hi);
-                if (rec0 != find_rec(start, n, lo))
-                    return fail("running first record", t, rec0, find_rec(start, n, lo));
-                const uint64_t *s = start.data() + rec0;
-                uint64_t m = 0;
-                while (s[m] < hi)
-                    ++m;
-                if (m > T / 24 + 2 || (m == 0 && rec0 != 0))
-                    return fail("records of a tile", t, m, T);
-                for (uint64_t p = lo; p < hi; p += 8) {
-                    const uint64_t j = find_rec(s, m, p);
-                    uint64_t rel;
-                    if (!word_in_rec(recs[rec0 + j], s[j], p, &rel))
-                        continue; /* a commit record's word */
-                    const Piece pc = piece_at(recs[rec0 + j], rel);
-                    out[p / 8] = pc.n ? gather8(src + pc.src_off, pc.n) : pc.word;
-                    ++written;
-                }
-                rec0 += s[m] == hi ? m : m ? m - 1 : 0;
-            }
-        }
-        if (written != P[n] / 8)
-            return fail("words written", written, P[n] / 8, T);
+        if (n && sweep<0, true>(src, recs, start, T, base, tot.body_end, P[n] / 8, out, stores))
+            return 1;
         /* commits, the finalise commit, header */
         const uint8_t *ob = reinterpret_cast<const uint8_t *>(out.data());
         uint64_t w[3];
@@ -159,7 +113,7 @@ int main(int argc, char **argv)
             const uint64_t off = placed(base, first[t], C[t]);
             reg = crc_span(ob + off, slen[t]);
             const int k = commit_words(reg, slen[t], false, w, &stored);
-            if ((uint64_t)k * 8 != commit_len(slen[t]) || out[(off + slen[t]) / 8] != 0xA5A5A5A5A5A5A5A5ull)
+            if ((uint64_t)k * 8 != commit_len(slen[t]) || out[(off + slen[t]) / 8] != CANARY)
                 return fail("commit record", t, off, slen[t]);
             for (int i = 0; i < k; ++i)
                 out[(off + slen[t]) / 8 + i] = w[i];
@@ -179,11 +133,12 @@ int main(int argc, char **argv)
                 ++d;
             return fail("byte differs at, tile, file", d, T, file_len);
         }
-        if (out[file_len / 8] != 0xA5A5A5A5A5A5A5A5ull)
+        if (out[file_len / 8] != CANARY)
             return fail("word past the end written", T, file_len, 0);
     }
     free(buf);
-    printf("ok %llu records %llu commits %llu bytes\n", (unsigned long long)n, (unsigned long long)tot.commits,
-           (unsigned long long)file_len);
+    printf("ok %llu records %llu commits %llu bytes; stores: %llu of 16 bytes, %llu of a first half, %llu of a second half\n",
+           (unsigned long long)n, (unsigned long long)tot.commits, (unsigned long long)file_len,
+           (unsigned long long)stores.both, (unsigned long long)stores.first, (unsigned long long)stores.second);
     return 0;
 }

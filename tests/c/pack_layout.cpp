@@ -1,42 +1,28 @@
 /*
  * pack_layout.cpp -- the device packer's layout arithmetic on the CPU
- * (tests/test_pack_layout.py).  Includes only the header the kernels of
+ * (tests/test_pack_layout.py).  Includes only the headers the kernels of
  * zscrc_devpack.hip share with the host, reads a case file
  *
  *   u64 src_len, n, file_len, shift, startidx, endidx; uuid[16];
  *   src[src_len]; recs[n] (4 x u64); file[file_len] (the expected packed file)
  *
  * and rebuilds the file the way the kernels do: record lengths and starts,
- * the layout, then for each tile size the records region tile by tile and word
- * by word (find_rec, piece_at, gather8), the pointers, the two commit records
- * from bitwise span CRCs, the header.  The source lies at an address = shift
- * mod 8 in an allocation that ends with its last 8-byte granule, so a
- * sanitizer sees any read outside the aligned words that hold source bytes.
- * Exit status 0 = every byte equal at every tile size.
+ * the layout, then for each tile size the records region by the kernel's own
+ * tile sweep (copy_tiles_sweep.h) at four grid sizes, the pointers, the two
+ * commit records from bitwise span CRCs, the header.  The source lies at an
+ * address = shift mod 8 in an allocation that ends with its last 8-byte
+ * granule, so a sanitizer sees any read outside the aligned words that hold
+ * source bytes.
+ * Exit status 0 = every byte equal at every tile and grid size; the ok line
+ * counts the stores of each kind.
  */
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <vector>
 
-#include "../../zeroskip_amd/csrc/zscrc_pack_layout.h"
+static const char *PROGRAM = "pack_layout";
+#include "copy_tiles_sweep.h"
 
 using namespace zspack;
-
-static int fail(const char *what, uint64_t a, uint64_t b, uint64_t c)
-{
-    fprintf(stderr, "pack_layout: %s (%llu, %llu, %llu)\n", what, (unsigned long long)a, (unsigned long long)b,
-            (unsigned long long)c);
-    return 1;
-}
-
-static uint32_t crc_span(const uint8_t *p, uint64_t n)
-{
-    uint32_t c = 0;
-    for (uint64_t i = 0; i < n; ++i)
-        c = crc_bytes(c, p[i], 1);
-    return c;
-}
 
 int main(int argc, char **argv)
 {
@@ -73,40 +59,19 @@ int main(int argc, char **argv)
         return fail("file size", l.file_bytes, file_len, R);
 
     const uint64_t tiles[4] = {64, 128, 4096, 65536};
+    Stores stores{0, 0, 0};
     for (uint64_t T : tiles) {
         /* 8-byte words, so that the output is built the way the kernel stores it */
-        std::vector<uint64_t> out(file_len / 8 + 1, 0xA5A5A5A5A5A5A5A5ull);
-        uint64_t written = 0;
-        if (R) {
-            const uint64_t nt = tile_count(T, R);
-            uint64_t lo, hi;
-            tile_range(0, T, R, &lo, &hi);
-            uint64_t rec0 = find_rec(start, n, lo);
-            for (uint64_t t = 0; t < nt; ++t) {
-                tile_range(t, T, R, &lo, &hi);
-                if (lo >= hi || hi > R || (t + 1 == nt) != (hi == R))
-                    return fail("tile range", t, lo, hi);
-                if (rec0 != find_rec(start, n, lo))
-                    return fail("running first record", t, rec0, find_rec(start, n, lo));
-                const uint64_t *s = start.data() + rec0;
-                uint64_t m = 0;
-                while (s[m] < hi)
-                    ++m;
-                if (m == 0 || m > T / 24 + 2)
-                    return fail("records of a tile", t, m, T);
-                for (uint64_t p = lo; p < hi; p += 8) {
-                    if ((HDR + p) / T != t)
-                        return fail("word outside its tile", t, p, T);
-                    const uint64_t j = find_rec(s, m, p);
-                    const Piece pc = piece_at(recs[rec0 + j], p - s[j]);
-                    out[(HDR + p) / 8] = pc.n ? gather8(src + pc.src_off, pc.n) : pc.word;
-                    ++written;
-                }
-                rec0 += s[m] == hi ? m : m - 1;
-            }
+        std::vector<uint64_t> out(file_len / 8 + 1, CANARY);
+        if (R && sweep<HDR, false>(src, recs, start, T, HDR, HDR + R, R / 8, out, stores))
+            return 1;
+        /* the sweep's tiles in file coordinates are zscrc_pack_layout.h's in region coordinates */
+        for (uint64_t t = 0, lo, hi; R && t <= tile_count(T, R); ++t) {
+            tile_range(t, T, R, &lo, &hi);
+            if (t == tile_count(T, R) ? zstile::run_of(0, 1, T, HDR, HDR + R).t1 != t
+                                      : zstile::tile_lo(t, T, HDR) != HDR + lo || zstile::tile_hi(t, T, HDR + R) != HDR + hi)
+                return fail("tiles in file and in region coordinates", t, lo, hi);
         }
-        if (written != R / 8)
-            return fail("words written", written, R / 8, T);
         /* pointers and count, commits, header */
         out[l.ptr_off / 8] = mem_be64(n);
         for (uint64_t i = 0; i < n; ++i)
@@ -131,10 +96,12 @@ int main(int argc, char **argv)
                 ++at;
             return fail("byte differs at, tile, file", at, T, file_len);
         }
-        if (out[file_len / 8] != 0xA5A5A5A5A5A5A5A5ull)
+        if (out[file_len / 8] != CANARY)
             return fail("word past the file written", T, file_len, 0);
     }
     free(buf);
-    printf("ok %llu records %llu bytes\n", (unsigned long long)n, (unsigned long long)file_len);
+    printf("ok %llu records %llu bytes; stores: %llu of 16 bytes, %llu of a first half, %llu of a second half\n",
+           (unsigned long long)n, (unsigned long long)file_len, (unsigned long long)stores.both,
+           (unsigned long long)stores.first, (unsigned long long)stores.second);
     return 0;
 }

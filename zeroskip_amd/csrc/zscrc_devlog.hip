@@ -25,11 +25,9 @@
  *                       before it, and the span descriptors in file offsets
  *   log_starts_kernel   one thread per record: its start P[i] + C[tx_of(i)] in
  *                       the file (in place of P[i]) and its listed entry
- *   log_copy_kernel     the hot path: output tiles in file coordinates, the
- *                       starts of a tile's records in LDS, every thread builds
- *                       aligned 16-byte words out of generated header words,
- *                       padding and gathered source bytes; the words of commit
- *                       records are left to the seal
+ *   log_copy_kernel     the hot path: the records by the tile sweep that the
+ *                       packer shares (zscrc_copy_tiles.h); the words of
+ *                       commit records are left to the seal
  *   (the library's variable-length batch over the span descriptors)
  *   log_seal_kernel     one thread per commit: its record from the span's CRC,
  *                       the finalise commit, the header, the result words
@@ -43,6 +41,7 @@
 #include <cstdint>
 
 #include "../../include/zscrc.h"
+#include "zscrc_copy_tiles.h"
 #include "zscrc_internal.h"
 #include "zscrc_log_layout.h"
 #include "zscrc_wg.h"
@@ -51,12 +50,7 @@ namespace {
 
 using namespace zspack;
 using namespace zsdev;
-
-constexpr uint64_t DEF_TILE = 65536, TILE_MIN = 64, TILE_MAX = 65536;
-/* starts of a tile's records in LDS, as pack_copy_kernel keeps them: a record
- * is 24 bytes at least, commit records in between only make them fewer */
-constexpr uint32_t LDS_STARTS = ((uint32_t)(TILE_MAX / 24) + 3 + WG - 1) / WG * WG + WG;
-constexpr unsigned COPY_WG_PER_CU = 6;
+using namespace zstile;
 
 enum { SC_BAD = 0, SC_BADTX = 1, SC_CODE = 2, SC_BODY_END = 3, SC_WORDS = 8 };
 
@@ -292,85 +286,16 @@ __global__ __launch_bounds__(WG) void log_starts_kernel(Log a)
         a.new_recs[i] = zslog::listed(a.recs[i], st);
 }
 
-/* The word at rel of record r: generated, or gathered from the source. */
-__device__ inline uint64_t record_word(const Log &a, const zscrc_zs_record &r, uint64_t rel)
-{
-    const Piece pc = piece_at(r, rel);
-    return pc.n ? gather8(a.src + pc.src_off, pc.n) : pc.word;
-}
-
+/* The records in [base, body end) by zscrc_copy_tiles.h's sweep: the starts
+ * are file offsets, and the words of the commit records in between are left
+ * to the seal. */
 __global__ __launch_bounds__(WG) void log_copy_kernel(Log a)
 {
     __shared__ uint64_t s_start[LDS_STARTS];
     if (a.sc[SC_CODE] != 0)
         return;
-    /* records lie in [base, stop); stop > base: there is a record */
-    const uint64_t base = zslog::base_of(a.at), stop = a.sc[SC_BODY_END];
-    const uint64_t T = a.tile, tlo = base / T, thi = (stop + T - 1) / T;
-    const uint64_t per = (thi - tlo + gridDim.x - 1) / gridDim.x;
-    const uint64_t t0 = tlo + (uint64_t)blockIdx.x * per;
-    const uint64_t t1 = t0 + per < thi ? t0 + per : thi;
-    if (t0 >= t1)
-        return;
-    /* the last record that starts at or before the run's first byte (record 0
-     * where commits of empty transactions come first) */
-    uint64_t rec0 = find_rec(a.start, a.n, t0 * T > base ? t0 * T : base);
-    for (uint64_t t = t0; t < t1; ++t) {
-        const uint64_t f0 = t * T, hi = f0 + T < stop ? f0 + T : stop;
-        /* s_start[j] = start[rec0 + j] up to the first one at or past hi (start[n] = stop is) */
-        uint32_t m = 0;
-        for (uint32_t b = 0; b < LDS_STARTS; b += WG) {
-            const uint64_t idx = rec0 + b + threadIdx.x;
-            const uint64_t s = a.start[idx < a.n ? idx : a.n];
-            s_start[b + threadIdx.x] = s;
-            const uint32_t c = (uint32_t)__syncthreads_count(s < hi);
-            m += c;
-            if (c < WG)
-                break;
-        }
-        /* 16-byte words of the tile at file offset f: a half before base, at or
-         * past hi, or in a commit record is not this kernel's to write */
-        for (uint64_t w = threadIdx.x; w < T / 16; w += WG) {
-            const uint64_t f = f0 + 16 * w;
-            if (f + 16 <= base)
-                continue;
-            if (f >= hi)
-                break;
-            const bool in0 = f >= base, in1 = f + 8 < hi;
-            /* one search a 16-byte word: its second half lies behind the same
-             * start or, where the next record starts in between, at that one */
-            uint64_t j = find_rec(s_start, m, in0 ? f : f + 8);
-            zscrc_zs_record r = a.recs[rec0 + j];
-            uint64_t v0 = 0, v1 = 0, rel;
-            bool h0 = false, h1 = false;
-            if (in0) {
-                h0 = zslog::word_in_rec(r, s_start[j], f, &rel);
-                if (h0)
-                    v0 = record_word(a, r, rel);
-                if (in1 && f + 8 >= s_start[j + 1])
-                    r = a.recs[rec0 + ++j];
-            }
-            if (in1) {
-                h1 = zslog::word_in_rec(r, s_start[j], f + 8, &rel);
-                if (h1)
-                    v1 = record_word(a, r, rel);
-            }
-            if (h0 && h1) {
-                u64x2 v;
-                v.x = v0;
-                v.y = v1;
-                *reinterpret_cast<u64x2 *>(a.out + f) = v;
-            } else if (h0) {
-                *reinterpret_cast<uint64_t *>(a.out + f) = v0;
-            } else if (h1) {
-                *reinterpret_cast<uint64_t *>(a.out + f + 8) = v1;
-            }
-        }
-        /* the next tile starts at hi: behind start[rec0 + m - 1], or at rec0 + m's first byte */
-        const bool at_start = s_start[m] == hi;
-        __syncthreads(); /* s_start is rewritten by the next tile */
-        rec0 += at_start ? m : m ? m - 1 : 0;
-    }
+    /* stop > base: there is a record */
+    copy_tiles<0, true>(a.src, a.recs, a.start, a.n, a.out, a.tile, zslog::base_of(a.at), a.sc[SC_BODY_END], s_start);
 }
 
 __global__ __launch_bounds__(WG) void log_seal_kernel(Log a, Header h)

@@ -18,13 +18,8 @@
  *                       the count that heads the pointer section
  *   pack_prefix_kernel  one workgroup per block: each record's start in the
  *                       region (8 bytes a record) and its big-endian pointer
- *   pack_copy_kernel    the hot path: the file is cut into output tiles; a
- *                       workgroup takes a run of consecutive tiles, finds the
- *                       first record that reaches into it by binary search,
- *                       keeps the starts of a tile's records in LDS, and every
- *                       thread builds whole aligned 16-byte output words out
- *                       of generated header words, padding and source bytes
- *                       gathered from any alignment
+ *   pack_copy_kernel    the hot path: the records region by the tile sweep
+ *                       that the log writer shares (zscrc_copy_tiles.h)
  *   (the library's variable-length batch over the two span descriptors)
  *   pack_seal_kernel    one lane: the two commit records from the span CRCs,
  *                       the header, the result words [4..7]
@@ -44,6 +39,7 @@
 #include <cstdint>
 
 #include "../../include/zscrc.h"
+#include "zscrc_copy_tiles.h"
 #include "zscrc_internal.h"
 #include "zscrc_pack_layout.h"
 #include "zscrc_wg.h"
@@ -52,17 +48,7 @@ namespace {
 
 using namespace zspack;
 using namespace zsdev;
-
-constexpr uint64_t DEF_TILE = 65536, TILE_MIN = 64, TILE_MAX = 65536;
-/* starts of a tile's records in LDS: the most records that reach into a tile
- * (24 bytes each at least), one more for the end, rounded up to whole rounds
- * of WG loads */
-constexpr uint32_t LDS_STARTS = ((uint32_t)(TILE_MAX / 24) + 3 + WG - 1) / WG * WG + WG;
-/* what the 24 KiB of starts admit on a CU: every workgroup of the copy is
- * resident, so the equal runs of tiles end together.  (An instance with 8 KiB
- * of starts for tiles up to 16 KiB, eight workgroups a CU, was measured and
- * was no faster there: DESIGN.md 2.6.) */
-constexpr unsigned COPY_WG_PER_CU = 6;
+using namespace zstile;
 
 /* scratch: SC_WORDS words, then nblocks + 1 block sums, then n + 1 starts */
 enum { SC_BAD = 0, SC_CODE = 1, SC_REGION = 2, SC_PTR_OFF = 3, SC_DOFF = 4, SC_DLEN = 6, SC_CRC = 8, SC_WORDS = 16 };
@@ -173,13 +159,8 @@ __global__ __launch_bounds__(WG) void pack_prefix_kernel(Pack a)
     }
 }
 
-/* The word at rel of record r: generated, or gathered from the source. */
-__device__ inline uint64_t record_word(const Pack &a, const zscrc_zs_record &r, uint64_t rel)
-{
-    const Piece pc = piece_at(r, rel);
-    return pc.n ? gather8(a.src + pc.src_off, pc.n) : pc.word;
-}
-
+/* The records region [40, 40 + region) by zscrc_copy_tiles.h's sweep: the
+ * starts are region coordinates, and the records fill the region. */
 __global__ __launch_bounds__(WG) void pack_copy_kernel(Pack a)
 {
     __shared__ uint64_t s_start[LDS_STARTS];
@@ -188,68 +169,7 @@ __global__ __launch_bounds__(WG) void pack_copy_kernel(Pack a)
     const uint64_t region = a.sc[SC_REGION];
     if (region == 0)
         return;
-    const uint64_t T = a.tile, ntiles = tile_count(T, region);
-    const uint64_t per = (ntiles + gridDim.x - 1) / gridDim.x;
-    const uint64_t t0 = (uint64_t)blockIdx.x * per;
-    const uint64_t t1 = t0 + per < ntiles ? t0 + per : ntiles;
-    if (t0 >= t1)
-        return;
-    uint64_t lo, hi;
-    tile_range(t0, T, region, &lo, &hi);
-    /* the first record that reaches into the run's first tile */
-    uint64_t rec0 = find_rec(a.start, a.n, lo);
-    for (uint64_t t = t0; t < t1; ++t) {
-        tile_range(t, T, region, &lo, &hi);
-        /* s_start[j] = start[rec0 + j] up to the first one at or past hi (start[n] = region is) */
-        uint32_t m = 0;
-        for (uint32_t base = 0; base < LDS_STARTS; base += WG) {
-            const uint64_t idx = rec0 + base + threadIdx.x;
-            const uint64_t s = a.start[idx < a.n ? idx : a.n];
-            s_start[base + threadIdx.x] = s;
-            const uint32_t c = (uint32_t)__syncthreads_count(s < hi);
-            m += c;
-            if (c < WG)
-                break;
-        }
-        /* 16-byte words of the tile, file offset f; the region is [40, 40 + region):
-         * a word half outside it is an 8-byte store of the half inside */
-        const uint64_t f0 = t * T;
-        for (uint64_t w = threadIdx.x; w < T / 16; w += WG) {
-            const uint64_t f = f0 + 16 * w;
-            if (f + 16 <= HDR)
-                continue;
-            if (f >= HDR + hi)
-                break;
-            const bool in0 = f >= HDR, in1 = f + 8 < HDR + hi;
-            /* one search a 16-byte word: its second half lies in the same
-             * record or, where that ends in between, at the next one's start */
-            const uint64_t p = in0 ? f - HDR : f + 8 - HDR;
-            uint64_t j = find_rec(s_start, m, p);
-            zscrc_zs_record r = a.recs[rec0 + j];
-            uint64_t v0 = 0, v1 = 0;
-            if (in0) {
-                v0 = record_word(a, r, p - s_start[j]);
-                if (in1 && p + 8 >= s_start[j + 1])
-                    r = a.recs[rec0 + ++j];
-            }
-            if (in1)
-                v1 = record_word(a, r, f + 8 - HDR - s_start[j]);
-            if (in0 && in1) {
-                u64x2 v;
-                v.x = v0;
-                v.y = v1;
-                *reinterpret_cast<u64x2 *>(a.out + f) = v;
-            } else if (in0) {
-                *reinterpret_cast<uint64_t *>(a.out + f) = v0;
-            } else {
-                *reinterpret_cast<uint64_t *>(a.out + f + 8) = v1;
-            }
-        }
-        /* the next tile starts at hi: in record rec0 + m - 1, or at rec0 + m's first byte */
-        const bool at_start = s_start[m] == hi;
-        __syncthreads(); /* s_start is rewritten by the next tile */
-        rec0 += at_start ? m : m - 1;
-    }
+    copy_tiles<HDR, false>(a.src, a.recs, a.start, a.n, a.out, a.tile, HDR, HDR + region, s_start);
 }
 
 __global__ __launch_bounds__(64) void pack_seal_kernel(Pack a, Header h)

@@ -76,7 +76,9 @@ ZSREC_HD inline Layout layout(uint64_t n, uint64_t region)
 
 /* Output tiles: tile t is the file offsets [t * tile, (t + 1) * tile) cut to
  * the records region, so every 16-byte word of a tile is 16-byte aligned in a
- * 16-byte aligned output.  In region coordinates (file offset - 40): */
+ * 16-byte aligned output.  In region coordinates (file offset - 40); the copy
+ * itself sweeps in file coordinates (zscrc_copy_tiles.h), and
+ * tests/c/pack_layout.cpp holds the two against each other: */
 ZSREC_HD inline uint64_t tile_count(uint64_t tile, uint64_t region) { return (HDR + region + tile - 1) / tile; }
 ZSREC_HD inline void tile_range(uint64_t t, uint64_t tile, uint64_t region, uint64_t *lo, uint64_t *hi)
 {
