@@ -10,10 +10,9 @@ from bisect import bisect_left
 import numpy as np
 
 from tests import merge_cases as mc
+from tests.images import EINVAL64, U64_MAX  # noqa: F401  (the tests read them as fc.*)
 
-U64_MAX = (1 << 64) - 1
 NONE, BAD_QUERY = U64_MAX, U64_MAX - 1
-EINVAL64 = U64_MAX  # (uint64_t)(int64_t)ZSCRC_EINVAL
 
 
 def recs_of(r) -> np.ndarray:

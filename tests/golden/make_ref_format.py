@@ -26,6 +26,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from oracle import zs_format as zf  # noqa: E402
+from tests.images import UUIDSTR  # noqa: E402  (the repack fixtures' DB uuid, bytes 0..15)
 
 DEMO = os.path.join(ROOT, "oracle", "_ref", "format_demo")
 OUTDIR = os.path.join(ROOT, "tests", "golden", "ref_format")
@@ -280,9 +281,6 @@ def ref_merge_packed(sources):
             out.append(it["recs"][it["pos"]])
         step(it)
     return out
-
-
-UUIDSTR = "00010203-0405-0607-0809-0a0b0c0d0e0f"   # the repack fixtures' DB uuid (bytes 0..15)
 
 
 def repack1_inputs():

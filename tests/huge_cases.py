@@ -27,9 +27,9 @@ from tests import find_cases as fc
 from tests import gather_cases as gc
 from tests import merge_cases as mc
 from tests import scan_cases as sc
+from tests.images import U64_MAX
 from tests.pack_cases import long_delete_record
 
-U64_MAX = (1 << 64) - 1
 B31, B32 = 1 << 31, 1 << 32
 ODD_AT = B32 + (1 << 29) + 5
 ARENA_BYTES = B32 + (768 << 20) + 77

@@ -12,13 +12,11 @@ import numpy as np
 from oracle import zs_format as zf
 from tests import pack_cases as pc
 from tests import records_images as ri
+from tests.images import EINVAL64, OVERFLOW, U64_MAX  # noqa: F401  (the log tests read them as lc.*)
 from zeroskip_amd import zsfile
 
 UUID = bytes(range(16, 32))
-U64_MAX = (1 << 64) - 1
 SHORT = zf.MAX_SHORT_VAL_LEN
-EINVAL64 = U64_MAX  # (uint64_t)(int64_t)ZSCRC_EINVAL
-OVERFLOW = 3
 
 
 class Case:
@@ -93,6 +91,39 @@ def _span_starts_at(case, t, i):
     recs, rc = ri.host_records(case.want, zsfile.ACTIVE)
     assert why == "end" and all(c["ok"] for c in commits) and len(recs) == case.n
     assert commits[t]["span_off"] == int(recs[i, 0]) - 24, (case.name, t, i)
+
+
+def check_against_image(case, d, got: bytes):
+    """A writer's result (host twin or device): image, words and optional
+    outputs against the oracle's image and its listing."""
+    want = case.want
+    assert d["code"] == 0 and d["n"] == case.n and d["end"] == len(want), (case.name, d["code"], d["end"], len(want))
+    assert got[:len(want)] == want, case.name
+    assert d["written"] == len(want) - case.at and d["commits"] == case.n_commits
+    # what the lister and the walk find in the bytes written (the prefix cut off: offsets shifted back)
+    if case.at:
+        tail = zf.header_bytes(case.uuid, 0, 0) + want[case.at:]
+        shift = case.at - 40
+    else:
+        tail, shift = want, 0
+    recs, rc = ri.host_records(tail, zsfile.ACTIVE)
+    assert rc == zsfile.END and len(recs) == case.n, case.name
+    live = recs[:, 2] != U64_MAX
+    recs[:, 0] += np.uint64(shift)
+    recs[live, 2] += np.uint64(shift)
+    assert np.array_equal(np.asarray(d["new_recs"]).view(np.uint64).reshape(-1, 4), recs), case.name
+    off, ln, rc, end = zsfile.walk(tail)
+    assert rc == zsfile.END and end == len(tail) and len(off) == case.n_commits, case.name
+    assert np.array_equal(np.asarray(d["span_off"]).view(np.uint64), off + np.uint64(shift)), case.name
+    assert np.array_equal(np.asarray(d["span_len"]).view(np.uint64), ln), case.name
+    assert d["long_commits"] == sum(1 for o, l in zip(off, ln) if tail[int(o + l)] == zf.REC_LONG_COMMIT)
+    assert d["last_crc"] == case.writer.mf_crc32, case.name
+    stored = int.from_bytes(want[-4:], "big") if case.n_commits else 0
+    assert d["stored_crc"] == stored, case.name
+    nc = case.n_commits
+    with np.errstate(over="ignore"):
+        bound = zsfile.device_log_bound(case.n, nc, int(case.recs[:, 1].sum()), int(case.recs[case.recs[:, 2] != U64_MAX, 3].sum()))
+    assert bound + (case.at - 40 if case.at else 0) >= len(want), case.name
 
 
 # ------------------------------------------------------------------ small cases

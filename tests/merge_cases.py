@@ -7,8 +7,7 @@ import struct
 
 import numpy as np
 
-U64_MAX = (1 << 64) - 1
-OVERFLOW = 3
+from tests.images import OVERFLOW, U64_MAX  # noqa: F401  (the tests read them as mc.*)
 
 
 class Case:

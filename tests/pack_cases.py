@@ -10,11 +10,9 @@ import numpy as np
 from oracle import oracle
 from oracle import zs_format as zf
 from tests import records_images as ri
+from tests.images import REF as GOLDEN
+from tests.images import U64_MAX, UUID
 from zeroskip_amd import repack, zsfile
-
-UUID = bytes(range(16))
-U64_MAX = (1 << 64) - 1
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_format")
 
 
 class Case:
@@ -236,11 +234,23 @@ def small_cases():
         [regenerated_headers(), long_delete(), shared_bytes()]
 
 
+def records(n, seed, maxval=600, deletes=True):
+    """n (key, value or None) pairs in key order, every thirteenth a delete (the host packer's lists)."""
+    rng = np.random.default_rng(seed)
+    recs = []
+    for i in range(n):
+        key = b"%016d" % (i * 7)
+        if deletes and i % 13 == 4:
+            recs.append((key, None))
+        else:
+            recs.append((key, rng.integers(0, 256, int(rng.integers(0, maxval)), dtype=np.uint8).tobytes()))
+    return recs
+
+
 def long_commit_long_records():
     """The list of test_pack_long_commit_long_records (tests/test_gpu_repack.py):
     a 17 MiB value, a 70,000-byte key, an empty value, region above 16 MiB."""
-    from tests.test_gpu_repack import _records
-    pairs = _records(2500, 9, maxval=9000)
+    pairs = records(2500, 9, maxval=9000)
     big = np.random.default_rng(1).integers(0, 256, (17 << 20) + 3, dtype=np.uint8).tobytes()
     pairs.insert(100, (b"%016d" % 700 + b"+big", big))
     pairs.insert(200, (b"%016d" % 1400 + b"+long-key" + b"q" * 70000, b"v" * 33))

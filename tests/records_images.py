@@ -11,12 +11,10 @@ import numpy as np
 
 from oracle import zs_format as zf
 from tests import fuzzlib
-from tests.test_format_oracle import UUID, build_active
+from tests.images import U64_MAX, UUID, build_active
 from tests.walk_images import Img, short_commit
 from zeroskip_amd import repack, zsfile
 from zeroskip_amd._lib import lib
-
-U64_MAX = (1 << 64) - 1
 
 
 def host_records(img: bytes, kind: int):
@@ -231,3 +229,31 @@ def wellformed() -> bytes:
     recs, rc = host_records(img, zsfile.ACTIVE)
     assert rc == zsfile.END and len(img) > 16384 and 0 < int((recs[:, 2] == U64_MAX).sum()) < len(recs)
     return img
+
+
+def folds(h: np.ndarray):
+    """res[3..7] of a host record list."""
+    if len(h) == 0:
+        return [0, 0, 0, 0, 0]
+    with np.errstate(over="ignore"):
+        return [int((h[:, 2] == U64_MAX).sum()), int(h[:, 1].sum(dtype=np.uint64)), int(h[:, 3].sum(dtype=np.uint64)),
+                int(h[:, 1].max()), int(h[:, 3].max())]
+
+
+def unaligned_records_image(prefix: bytes):
+    """prefix + a key record of 4 key bytes whose value offset is 28 (its value
+    header right behind the key, at an offset = 4 mod 8) + a delete record, a
+    key / value record and a commit, all at offsets = 4 mod 8.  Returns (image,
+    the first unaligned offset, the records before the crafted one)."""
+    assert len(prefix) % 8 == 0
+    K = len(prefix)
+    rec = zf.be64((zf.REC_KEY << 56) | (4 << 40) | 28) + bytes(16) + b"key4" + \
+        zf.be64((zf.REC_VALUE << 56) | (5 << 32)) + zf.be64(0) + b"value" + bytes(3)
+    assert len(rec) == 52
+    tail = zf.delete_record(b"8bytekey") + zf.key_record(b"tail-key") + zf.value_record(b"t" * 13)
+    img = prefix + rec + tail + short_commit(len(tail))
+    before, _ = host_records(prefix, zsfile.ACTIVE)
+    h, rc = host_records(img, zsfile.ACTIVE)
+    assert rc == zsfile.END and len(h) == len(before) + 3 and (K + 52) % 8 == 4
+    assert [int(v) for v in h[len(before)]] == [K + 24, 4, K + 44, 5] and int(h[len(before) + 1][0]) == K + 52 + 24
+    return img, K + 52, len(before)

@@ -57,11 +57,11 @@ from tests import merge_cases as mc
 from tests import pack_cases as pc
 from tests import records_images as ri
 from tests import walk_images as wi
+from tests.images import U64_MAX
 from zeroskip_amd import repack, zsfile
 from zeroskip_amd._lib import lib
 
 NT = 4
-U64_MAX = (1 << 64) - 1
 WALK_BLOCK, WALK_TILE = 8192, 1024
 IDS, LEVEL_N, K = 20000, 10000, 3
 NQ, PAGES = 4096, (1, 8)

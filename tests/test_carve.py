@@ -7,26 +7,11 @@ aligned as asked, that the pieces are disjoint and in order and that the last
 one ends at bytes().  The program is built with the address and
 undefined-behaviour sanitizers and runs as its own process; nothing is
 preloaded and nothing of it is loaded into python.  No GPU."""
-import os
 import subprocess
 
-import pytest
+from tests import cprog
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "c", "carve.cpp")
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("carve") / "carve")
-    base = [os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", SRC, "-o", exe]
-    r = subprocess.run(base[:1] + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] + base[1:],
-                       capture_output=True, text=True)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        print("sanitizer build failed, building without:\n" + r.stderr[-2000:])
-        subprocess.run(base, check=True)
-    return exe, sanitized
+program = cprog.program_fixture("carve")
 
 
 def test_sanitizers_are_linked(program):

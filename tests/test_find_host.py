@@ -9,11 +9,8 @@ import pytest
 from oracle import zs_format as zf
 from tests import find_cases as fc
 from tests import merge_cases as mc
+from tests.images import REF, U64_MAX
 from zeroskip_amd import repack, zsfile
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "tests", "golden", "ref_format")
-U64_MAX = fc.U64_MAX
 
 
 def _same(case, check_order=False):

@@ -6,29 +6,15 @@ bucket and the bisection inside it -- at 1, 2, 64 and 2,048 splitters and
 compares the hits with the Python model's.  The program is built with the
 address and undefined-behaviour sanitizers and runs as its own process;
 nothing is preloaded and nothing of it is loaded into python.  No GPU."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cprog
 from tests import find_cases as fc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "c", "find_order.cpp")
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("find_order") / "find_order")
-    base = [os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", SRC, "-o", exe]
-    r = subprocess.run(base[:1] + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] + base[1:],
-                       capture_output=True, text=True)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        print("sanitizer build failed, building without:\n" + r.stderr[-2000:])
-        subprocess.run(base, check=True)
-    return exe, sanitized
+program = cprog.program_fixture("find_order")
 
 
 def _run(program, tmp_path, case, shift=0, qshift=0, want=None):

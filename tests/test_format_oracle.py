@@ -7,22 +7,7 @@ import numpy as np
 
 from oracle import oracle
 from oracle import zs_format as zf
-
-UUID = bytes(range(16))
-
-
-def build_active(ntx=50, seed=1):
-    rng = np.random.default_rng(seed)
-    w = zf.FileWriter(UUID, idx=3)
-    for t in range(ntx):
-        for _ in range(int(rng.integers(1, 4))):
-            k = b"%016d" % int(rng.integers(0, 10**9))
-            v = rng.integers(0, 256, int(rng.integers(0, 600)), dtype=np.uint8).tobytes()
-            w.add(k, v)
-        if t % 7 == 3:
-            w.remove(b"%016d" % t)       # zeroskip.c:985 quirk: span restarts here
-        w.commit()
-    return w.image()
+from tests.images import UUID, build_active
 
 
 def test_header_roundtrip():

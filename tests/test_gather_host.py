@@ -11,11 +11,10 @@ from oracle import oracle
 from oracle import zs_format as zf
 from tests import find_cases as fc
 from tests import gather_cases as gc
+from tests.images import REF
 from zeroskip_amd import repack, zsfile
 from zeroskip_amd._lib import lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "tests", "golden", "ref_format")
 CANARY = 0xA5
 
 

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
-from tests.test_consistent_host import OracleBackend, name, small_db
+from tests.consistent_cases import OracleBackend, name, small_db
 from zeroskip_amd import consistent as cs
 
 pytestmark = pytest.mark.gpu

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import zs_format as zf
-from tests.test_format_oracle import UUID, build_active
+from tests.images import UUID, build_active
 from zeroskip_amd import zsfile
 
 pytestmark = pytest.mark.gpu

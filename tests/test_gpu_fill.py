@@ -11,13 +11,12 @@ import torch
 
 from oracle import oracle
 from oracle import zs_format as zf
-from tests.test_gpu_runs import _zsbench_db
+from tests.images import UUID
+from tests.images import zsbench_db as _zsbench_db
 from zeroskip_amd import zsfile
 from zeroskip_amd._lib import ZscrcError
 
 pytestmark = pytest.mark.gpu
-
-UUID = bytes(range(16))
 
 
 def _blank(img, commits):

@@ -10,60 +10,32 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import find_cases as fc
+from tests.devmem import CANARY
+from tests.images import REF, U64_MAX, UUIDSTR
 from zeroskip_amd import zsfile
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "tests", "golden", "ref_format")
-U64_MAX = fc.U64_MAX
-CANARY = 0xA5
-PAD = 4096
 SPLITS = [1, 2, 64, 2048, 0]      # no table, the smallest, a middle one, the largest, the default
-
-
-def _dev_bytes(b: bytes, dev, shift: int = 0) -> torch.Tensor:
-    """The bytes in device memory at an address = shift mod 16 (an empty tensor for none)."""
-    buf = torch.zeros(len(b) + 32, dtype=torch.uint8, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    d = buf[shift:shift + len(b)]
-    if len(b):
-        d.copy_(torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()))
-    return d
-
-
-def _dev_recs(recs: np.ndarray, dev) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(recs).view(np.int64).reshape(-1, 4).copy()).to(dev)
-
-
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
-
-
-def _dev_in(case, dev, shift=0, qshift=0):
-    return (_dev_bytes(case.src, dev, shift), [(_dev_recs(r, dev), b) for r, b in case.levels],
-            _dev_bytes(case.qsrc, dev, qshift), _dev_recs(case.queries, dev))
 
 
 def _find(case, dev, splitters=0, check_order=False, scratch=None, dev_in=None, shift=0, qshift=0):
     """device_find into canary rows between fences: (hits uint64 [nq, 4], res uint64 [8])."""
-    d_src, levels, d_qsrc, queries = dev_in or _dev_in(case, dev, shift, qshift)
+    d_src, levels, d_qsrc, queries = dev_in or dm.dev_in(case, dev, shift, qshift)
     nq = int(queries.shape[0])
-    whole, out = _fenced(32 * nq, dev)
+    whole, out = dm.fenced(32 * nq, dev)
     res = torch.full((8,), -6, dtype=torch.int64, device=dev)
     zsfile.device_find(d_src, levels, d_qsrc, queries, check_order=check_order, splitters=splitters,
                        out=(out.view(torch.int64).view(nq, 4), res), scratch=scratch)
-    h = whole.cpu().numpy()
-    assert bool((h[:PAD] == CANARY).all() and (h[PAD + 32 * nq:] == CANARY).all()), case.name
-    return h[PAD:PAD + 32 * nq].view(np.uint64).reshape(nq, 4), res.cpu().numpy().view(np.uint64)
+    return dm.inside(whole, 32 * nq, case.name).view(np.uint64).reshape(nq, 4), res.cpu().numpy().view(np.uint64)
 
 
 def _same(case, dev, splits=SPLITS, check_order=False, shift=0, qshift=0, want=None):
     """The case at every table size: equal byte for byte, and equal to the model."""
     want, wres = want or case.model()
-    dev_in = _dev_in(case, dev, shift, qshift)
+    dev_in = dm.dev_in(case, dev, shift, qshift)
     for s in splits:
         got, r = _find(case, dev, s, check_order, dev_in=dev_in)
         what = (case.name, s, check_order, shift, qshift)
@@ -99,7 +71,7 @@ def test_query_counts(gpu, cases):
         sub = fc.FindCase("nq%d" % nq, c.src, c.levels, c.qsrc, c.queries[:nq])
         assert len(sub.queries) == nq
         _same(sub, gpu)
-    hits, res = zsfile.device_find(*_dev_in(fc.FindCase("nq0", c.src, c.levels, c.qsrc, c.queries[:0]), gpu))
+    hits, res = zsfile.device_find(*dm.dev_in(fc.FindCase("nq0", c.src, c.levels, c.qsrc, c.queries[:0]), gpu))
     assert tuple(hits.shape) == (0, 4) and [int(v) for v in res.cpu()] == [0] * 8
 
 
@@ -187,14 +159,14 @@ def test_records_outside_the_source(gpu, cases):
     c = cases["n194"]
     size, recs = len(c.src), c.levels[0][0]
     q = recs[[3, 60, 120]]
-    d_q, d_src = _dev_recs(q, gpu), _dev_bytes(c.src, gpu)
+    d_q, d_src = dm.dev_recs(q, gpu), dm.dev_bytes(c.src, gpu)
 
     def bad(changes, first, base=0):
         r = recs.copy()
         for i, col, v in changes:
             r[i, col] = v
         case = fc.FindCase("bad", c.src, [(q, 0), (r[:100], base), (r[100:], base)], c.src, q)
-        dev_in = (d_src, [(_dev_recs(x, gpu), b) for x, b in case.levels], d_src, d_q)
+        dev_in = (d_src, [(dm.dev_recs(x, gpu), b) for x, b in case.levels], d_src, d_q)
         for s in (1, 64):
             got, res = _find(case, gpu, s, dev_in=dev_in)
             assert [int(v) for v in res] == [fc.EINVAL64, 3 + first, 0, 0, 0, 0, 0, 0], (changes, s, res)
@@ -235,18 +207,17 @@ def test_check_order(gpu, cases):
     equal[41] = equal[40]
     for r, first in ((swapped, 31), (equal, 41)):
         case = fc.FindCase("unsorted", c.src, [(recs[:7], 0), (r, 0)], c.qsrc, c.queries)   # seq counts level 0's 7
-        dev_in = _dev_in(case, gpu)
+        dev_in = dm.dev_in(case, gpu)
         for s in (1, 2, 64):
             got, res = _find(case, gpu, s, check_order=True, dev_in=dev_in)
             assert [int(v) for v in res] == [fc.EINVAL64, 7 + first, 0, 0, 0, 0, 0, 1], (s, res)
             assert bool((got.view(np.uint8) == CANARY).all())
             # without the flag the list is searched all the same, inside its bounds; the hits are unspecified
             need = zsfile.device_find_scratch_bytes(2, s)
-            whole, scratch = _fenced(need, gpu)
+            whole, scratch = dm.fenced(need, gpu)
             got, res = _find(case, gpu, s, scratch=scratch, dev_in=dev_in)
             assert int(res[0]) == 0 and int(res[1]) == len(c.queries) and sum(int(v) for v in res[2:6]) == int(res[1])
-            h = whole.cpu().numpy()
-            assert bool((h[:PAD] == CANARY).all() and (h[PAD + need:] == CANARY).all())
+            assert dm.intact(whole, need)
     # a bounds offence takes precedence over an earlier order offence
     r = swapped.copy()
     r[50, 1] = U64_MAX
@@ -262,19 +233,18 @@ def test_caller_scratch_fenced(gpu, cases):
         c = cases[name]
         need = zsfile.device_find_scratch_bytes(len(c.levels), s)
         assert need > 0
-        whole, scratch = _fenced(need, gpu)
+        whole, scratch = dm.fenced(need, gpu)
         assert scratch.data_ptr() % 16 == 0
         want, wres = c.model()
         got, r = _find(c, gpu, s, scratch=scratch)
         assert [int(v) for v in r] == wres and got.tobytes() == want.tobytes(), name
-        h = whole.cpu().numpy()
-        assert bool((h[:PAD] == CANARY).all() and (h[PAD + need:] == CANARY).all()), name
+        assert dm.intact(whole, need), name
 
 
 def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     """A walk and a lookup on two streams share the library's scratch, ordered by its event."""
     from tests import records_images as ri
-    d_img = _dev_bytes(ri.wellformed(), gpu)
+    d_img = dm.dev_bytes(ri.wellformed(), gpu)
 
     def listed(walked):
         off, ln, res = (t.cpu().numpy() for t in walked)
@@ -283,7 +253,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     want_walk = listed(zsfile.device_walk(d_img))
     assert want_walk[2][1] > 0
     c = cases["n194"]
-    dev_in = _dev_in(c, gpu)
+    dev_in = dm.dev_in(c, gpu)
     s1, s2 = torch.cuda.Stream(device=gpu), torch.cuda.Stream(device=gpu)
     torch.cuda.synchronize(gpu)
     want, wres = c.model()
@@ -301,7 +271,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
 def test_two_runs_bit_for_bit(gpu, cases):
     for name, s in (("n194", 64), ("key_lengths", 0), ("deletes", 2)):
         c = cases[name]
-        dev_in = _dev_in(c, gpu)
+        dev_in = dm.dev_in(c, gpu)
         a = _find(c, gpu, s, dev_in=dev_in)
         b = _find(c, gpu, s, dev_in=dev_in)
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
@@ -310,7 +280,7 @@ def test_two_runs_bit_for_bit(gpu, cases):
 # -------------------------------------------------------------- reference fixture
 def test_reference_packed_file(gpu):
     img = open(os.path.join(REF, "packed.zs"), "rb").read()
-    d_img = _dev_bytes(img, gpu)
+    d_img = dm.dev_bytes(img, gpu)
     recs, rres = zsfile.device_records(d_img, zsfile.PACKED)
     n = int(rres[1])
     level = recs[:n].contiguous()
@@ -319,7 +289,7 @@ def test_reference_packed_file(gpu):
     host_level = level.cpu().numpy().view(np.uint64)
     near = [k + b"\x00" for k in keys] + [k[:-1] for k in keys if k]
     qsrc, queries = fc.lay_queries(near, residue=5)
-    d_qsrc, d_q = _dev_bytes(qsrc, gpu), _dev_recs(queries, gpu)
+    d_qsrc, d_q = dm.dev_bytes(qsrc, gpu), dm.dev_recs(queries, gpu)
     for s in SPLITS:
         # every key at its own index: the level is its own query list
         hits, res = zsfile.device_find(d_img, [(level, 0)], d_img, level, splitters=s, check_order=True)
@@ -336,12 +306,11 @@ def test_reference_packed_file(gpu):
 def test_reference_repack_inputs_as_levels(gpu):
     """repack2's two packed files as levels, the newer first: every key of either file."""
     d = os.path.join(REF, "repack2")
-    uuid = "00010203-0405-0607-0809-0a0b0c0d0e0f"
-    newer = open(os.path.join(d, "zeroskip-%s-8-9" % uuid), "rb").read()
-    older = open(os.path.join(d, "zeroskip-%s-4-7" % uuid), "rb").read()
+    newer = open(os.path.join(d, "zeroskip-%s-8-9" % UUIDSTR), "rb").read()
+    older = open(os.path.join(d, "zeroskip-%s-4-7" % UUIDSTR), "rb").read()
     arena = newer + bytes(-len(newer) % 64) + older
     at = [0, len(arena) - len(older)]
-    d_arena = _dev_bytes(arena, gpu)
+    d_arena = dm.dev_bytes(arena, gpu)
     levels = []
     for off, img in zip(at, (newer, older)):
         recs, res = zsfile.device_records(d_arena[off:off + len(img)], zsfile.PACKED)
@@ -356,7 +325,7 @@ def test_reference_repack_inputs_as_levels(gpu):
     values.update(dict(zf.packed_records(newer)))
     for k, (_, _, vo, vl) in zip(keys, want.tolist()):
         assert (None if vo == U64_MAX else arena[vo:vo + vl]) == values[k]
-    d_qsrc, d_q = _dev_bytes(qsrc, gpu), _dev_recs(queries, gpu)
+    d_qsrc, d_q = dm.dev_bytes(qsrc, gpu), dm.dev_recs(queries, gpu)
     for s in SPLITS:
         hits, res = zsfile.device_find(d_arena, levels, d_qsrc, d_q, splitters=s, check_order=True)
         assert hits.cpu().numpy().view(np.uint64).tobytes() == want.tobytes()
@@ -385,8 +354,8 @@ def test_a_million_records_and_a_million_queries(gpu):
     want[found, 2] = recs[at[found], 2]
     nf = int(found.sum())
     assert 0.4 * nq < nf < 0.6 * nq and int(at.max()) == n
-    d_src, d_recs = torch.from_numpy(src).to(gpu), _dev_recs(recs, gpu)
-    d_qsrc, d_q = torch.from_numpy(qv.astype(">u8").view(np.uint8)).to(gpu), _dev_recs(queries, gpu)
+    d_src, d_recs = torch.from_numpy(src).to(gpu), dm.dev_recs(recs, gpu)
+    d_qsrc, d_q = torch.from_numpy(qv.astype(">u8").view(np.uint8)).to(gpu), dm.dev_recs(queries, gpu)
     for s in (0, 1, 2048):
         hits, res = zsfile.device_find(d_src, [(d_recs, 0)], d_qsrc, d_q, splitters=s, check_order=True)
         assert [int(v) for v in res.cpu()] == [0, nq, nf, 0, nq - nf, 0, 0, 0]

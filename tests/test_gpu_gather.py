@@ -12,61 +12,34 @@ import torch
 
 from oracle import oracle
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import find_cases as fc
 from tests import gather_cases as gc
+from tests.devmem import CANARY
+from tests.images import REF
 from zeroskip_amd import zsfile
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "tests", "golden", "ref_format")
-CANARY = 0xA5
-PAD = 4096
 TILES = [64, 1024, 0]       # the smallest, a middle one, the default
 SLACK = 48                  # room behind the total that must stay untouched
-
-
-def _dev_bytes(b: bytes, dev, shift: int = 0) -> torch.Tensor:
-    """The bytes in device memory at an address = shift mod 16 (an empty tensor for none)."""
-    buf = torch.zeros(len(b) + 32, dtype=torch.uint8, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    d = buf[shift:shift + len(b)]
-    if len(b):
-        d.copy_(torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()))
-    return d
-
-
-def _dev_items(items: np.ndarray, dev) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(items).view(np.int64).reshape(-1, 4).copy()).to(dev)
-
-
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
-
-
-def _inside(whole: torch.Tensor, nbytes: int, what) -> np.ndarray:
-    """The fenced buffer's inside on the host, its fences checked."""
-    h = whole.cpu().numpy()
-    assert bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all()), what
-    return h[PAD:PAD + nbytes]
 
 
 def _gather(d_src, d_items, cap, tile=0, crcs=True, scratch=None, out_null=False):
     """device_gather into canary buffers between fences: (out uint8 [cap], offs
     uint64 [nq + 1], crcs uint32 [nq], res [8]) as they are afterwards."""
     dev, nq = d_src.device, int(d_items.shape[0])
-    w_out, out = _fenced(cap, dev)
-    w_offs, offs = _fenced(8 * (nq + 1), dev)
-    w_crc, crc = _fenced(4 * nq, dev)
+    w_out, out = dm.fenced(cap, dev)
+    w_offs, offs = dm.fenced(8 * (nq + 1), dev)
+    w_crc, crc = dm.fenced(4 * nq, dev)
     res = torch.full((8,), -6, dtype=torch.int64, device=dev)
     assert out.data_ptr() % 16 == 0
     zsfile.device_gather(d_src, d_items, cap=0 if out_null else cap, tile_bytes=tile, scratch=scratch,
                          out=(None if out_null else out, offs.view(torch.int64),
                               crc.view(torch.int32) if crcs else None, res))
     what = (nq, cap, tile)
-    return (_inside(w_out, cap, what), _inside(w_offs, 8 * (nq + 1), what).view(np.uint64),
-            _inside(w_crc, 4 * nq, what).view(np.uint32), [int(v) for v in res.cpu().numpy().view(np.uint64)])
+    return (dm.inside(w_out, cap, what), dm.inside(w_offs, 8 * (nq + 1), what).view(np.uint64),
+            dm.inside(w_crc, 4 * nq, what).view(np.uint32), [int(v) for v in res.cpu().numpy().view(np.uint64)])
 
 
 def _same(case, dev, tiles=TILES, shift=0, host=True, want=None):
@@ -74,7 +47,7 @@ def _same(case, dev, tiles=TILES, shift=0, host=True, want=None):
     each other), and to the host twin; nothing written at or past the total."""
     values, offs, crcs, res = want or case.model()
     total = res[3]
-    d_src, d_items = _dev_bytes(case.src, dev, shift), _dev_items(case.items, dev)
+    d_src, d_items = dm.dev_bytes(case.src, dev, shift), dm.dev_recs(case.items, dev)
     for t in tiles:
         out, o, c, r = _gather(d_src, d_items, total + SLACK, t)
         what = (case.name, t, shift)
@@ -102,7 +75,7 @@ def test_item_counts(gpu, cases):
         assert c.nq == n
         r = _same(c, gpu)
         assert r[2] + r[4] + r[5] + r[6] == r[1] == n
-    values, offs, crc, res = zsfile.device_gather(_dev_bytes(b"abc", gpu), _dev_items(gc.items_of([]), gpu), crcs=True)
+    values, offs, crc, res = zsfile.device_gather(dm.dev_bytes(b"abc", gpu), dm.dev_recs(gc.items_of([]), gpu), crcs=True)
     assert values.numel() == 0 and offs.cpu().tolist() == [0] and crc.numel() == 0 and res.cpu().tolist() == [0] * 8
 
 
@@ -190,14 +163,14 @@ def test_values_outside_the_source(gpu, cases):
     case = cases["n4097"]
     size = len(case.src)
     val = np.flatnonzero(gc.kinds(case.items)[0])
-    d_src = _dev_bytes(case.src, gpu)
+    d_src = dm.dev_bytes(case.src, gpu)
 
     def bad(changes, first):
         items = case.items.copy()
         for i, off, ln in changes:
             items[i, 2:] = (off, ln)
         assert gc.model(case.src, items)[3] == [gc.EINVAL64, first, 0, 0, 0, 0, 0, 0]
-        d_items = _dev_items(items, gpu)
+        d_items = dm.dev_recs(items, gpu)
         for t in (64, 0):
             out, offs, crc, res = _gather(d_src, d_items, 1 << 17, t)
             assert res == [gc.EINVAL64, first, 0, 0, 0, 0, 0, 0], (changes, t, res)
@@ -223,7 +196,7 @@ def test_overflow_and_the_sizing_call(gpu, cases):
     for case in (cases["n257"], gc.random_case(1)):
         values, offs, crcs, res = case.model()
         total = res[3]
-        d_src, d_items = _dev_bytes(case.src, gpu), _dev_items(case.items, gpu)
+        d_src, d_items = dm.dev_bytes(case.src, gpu), dm.dev_recs(case.items, gpu)
         for cap in (total - 1, 16):
             for t in (64, 0):
                 out, o, c, r = _gather(d_src, d_items, cap, t)
@@ -245,7 +218,7 @@ def test_without_crcs_the_same_values_and_offsets(gpu, cases):
     for name in ("n1025", "front", "misses_between"):
         case = cases[name]
         values, offs, _, res = case.model(crcs=False)
-        d_src, d_items = _dev_bytes(case.src, gpu), _dev_items(case.items, gpu)
+        d_src, d_items = dm.dev_bytes(case.src, gpu), dm.dev_recs(case.items, gpu)
         for t in TILES:
             out, o, c, r = _gather(d_src, d_items, res[3] + SLACK, t, crcs=False)
             assert r == res and o.tobytes() == offs.tobytes() and out[:res[3]].tobytes() == values.tobytes()
@@ -258,20 +231,20 @@ def test_caller_scratch_fenced(gpu, cases):
         case = cases[name]
         need = zsfile.device_gather_scratch_bytes(case.nq, t)
         assert need > 0
-        whole, scratch = _fenced(need, gpu)
+        whole, scratch = dm.fenced(need, gpu)
         assert scratch.data_ptr() % 16 == 0
         values, offs, crcs, res = case.model()
-        out, o, c, r = _gather(_dev_bytes(case.src, gpu), _dev_items(case.items, gpu), res[3] + SLACK, t,
+        out, o, c, r = _gather(dm.dev_bytes(case.src, gpu), dm.dev_recs(case.items, gpu), res[3] + SLACK, t,
                                scratch=scratch)
         assert r == res and o.tobytes() == offs.tobytes() and out[:res[3]].tobytes() == values.tobytes(), name
         assert c.tobytes() == crcs.tobytes(), name
-        _inside(whole, need, name)
+        dm.inside(whole, need, name)
 
 
 def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     """A walk and a gather on two streams share the library's scratch, ordered by its event."""
     from tests import records_images as ri
-    d_img = _dev_bytes(ri.wellformed(), gpu)
+    d_img = dm.dev_bytes(ri.wellformed(), gpu)
 
     def listed(walked):
         off, ln, res = (t.cpu().numpy() for t in walked)
@@ -281,7 +254,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     assert want_walk[2][1] > 0
     case = cases["n4097"]
     values, offs, crcs, res = case.model()
-    d_src, d_items = _dev_bytes(case.src, gpu), _dev_items(case.items, gpu)
+    d_src, d_items = dm.dev_bytes(case.src, gpu), dm.dev_recs(case.items, gpu)
     s1, s2 = torch.cuda.Stream(device=gpu), torch.cuda.Stream(device=gpu)
     torch.cuda.synchronize(gpu)
     for _ in range(3):
@@ -298,7 +271,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
 
 def test_two_runs_bit_for_bit(gpu, cases):
     for case, t in ((cases["n4097"], 64), (gc.random_case(3), 0), (cases["misses_between"], 1024)):
-        d_src, d_items = _dev_bytes(case.src, gpu), _dev_items(case.items, gpu)
+        d_src, d_items = dm.dev_bytes(case.src, gpu), dm.dev_recs(case.items, gpu)
         cap = case.model(crcs=False)[3][3] + SLACK
         a = _gather(d_src, d_items, cap, t)
         b = _gather(d_src, d_items, cap, t)
@@ -313,9 +286,9 @@ def test_device_get_on_the_find_cases(gpu):
     for case in fc.small_cases():
         want_hits, wres = case.model()
         values, offs, crcs, _ = gc.model(case.src, want_hits)
-        d_src = _dev_bytes(case.src, gpu)
-        levels = [(_dev_items(r, gpu), b) for r, b in case.levels]
-        d_qsrc, d_q = _dev_bytes(case.qsrc, gpu), _dev_items(case.queries, gpu)
+        d_src = dm.dev_bytes(case.src, gpu)
+        levels = [(dm.dev_recs(r, gpu), b) for r, b in case.levels]
+        d_qsrc, d_q = dm.dev_bytes(case.qsrc, gpu), dm.dev_recs(case.queries, gpu)
         for cap in (None, len(values) + 16):
             v, o, c, hits, fres, gres = zsfile.device_get(d_src, levels, d_qsrc, d_q, cap=cap, crcs=True)
             f = [int(x) for x in fres.cpu().numpy().view(np.uint64)]
@@ -334,7 +307,7 @@ def test_device_get_on_the_find_cases(gpu):
 def test_reference_packed_file_as_a_record_list(gpu):
     img = open(os.path.join(REF, "packed.zs"), "rb").read()
     pairs = zf.packed_records(img)
-    d_img = _dev_bytes(img, gpu)
+    d_img = dm.dev_bytes(img, gpu)
     recs, rres = zsfile.device_records(d_img, zsfile.PACKED)
     n = int(rres[1])
     assert n == len(pairs) > 100

@@ -25,6 +25,8 @@ import pytest
 import torch
 
 from oracle import oracle
+from tests import devmem as dm
+from tests.devmem import CANARY
 from zeroskip_amd._lib import check, lib
 
 pytestmark = pytest.mark.gpu
@@ -34,19 +36,6 @@ OPTS = [0, NO_RUNSPLIT, RO12, RO_LIST]
 OPT_IDS = ["default", "no_runsplit", "ro12", "ro_list"]
 T_KEY, T_COMMIT, T_FINAL, T_LONG_COMMIT, T_2ND = 1, 4, 16, 36, 8
 MAXLEN = 640
-PAD = 4096                # canary bytes on each side of every array
-CANARY = 0xA5
-
-
-def _fenced(nbytes: int, dev):
-    """(whole buffer, the nbytes slice in its middle) -- the rest canary."""
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
-
-
-def _intact(whole: torch.Tensor, nbytes: int) -> bool:
-    h = whole.cpu().numpy()
-    return bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all())
 
 
 def _build(n: int, seed: int):
@@ -139,9 +128,9 @@ def case(request, gpu):
     m = _build(n, 0xF00D + n)
     dev = gpu
     size = m["host"].nbytes
-    img_whole, img = _fenced(size, dev)
+    img_whole, img = dm.fenced(size, dev)
     img.copy_(torch.from_numpy(m["host"]))
-    seed_whole, seed = _fenced(4 * n, dev)
+    seed_whole, seed = dm.fenced(4 * n, dev)
     seed.copy_(torch.from_numpy(m["seeds"].view(np.uint8)))
     m.update(dev=dev, size=size, img_whole=img_whole, img=img, seed_whole=seed_whole, seed=seed,
              d_off=torch.from_numpy(m["offs"]).to(dev), d_len=torch.from_numpy(m["lens"].astype(np.int64)).to(dev))
@@ -159,8 +148,8 @@ def test_seeded_arrays_fenced(case, opt):
     the seeds or the arrays changes."""
     m = case
     n = m["n"]
-    cw, crc = _fenced(4 * n, m["dev"])
-    sw, st = _fenced(4 * n, m["dev"])
+    cw, crc = dm.fenced(4 * n, m["dev"])
+    sw, st = dm.fenced(4 * n, m["dev"])
     lib().zscrc_set_opt(opt)
     try:
         with torch.cuda.device(m["dev"]):
@@ -171,7 +160,7 @@ def test_seeded_arrays_fenced(case, opt):
     finally:
         lib().zscrc_set_opt(0)
     for whole, nb in ((cw, 4 * n), (sw, 4 * n), (m["img_whole"], m["size"]), (m["seed_whole"], 4 * n)):
-        assert _intact(whole, nb)
+        assert dm.intact(whole, nb)
     got_st = st.cpu().numpy().view(np.int32)
     got_crc = crc.cpu().numpy().view(np.uint32)
     assert np.array_equal(got_st, m["st"])
@@ -188,8 +177,8 @@ def test_seeded_verdict_fenced(case, opt):
     n = m["n"]
     want = set(np.nonzero(m["st"] != 1)[0].tolist())
     for cap in (4096, 7):
-        nw, nbad = _fenced(8, m["dev"])
-        bw, bad = _fenced(8 * cap, m["dev"])
+        nw, nbad = dm.fenced(8, m["dev"])
+        bw, bad = dm.fenced(8 * cap, m["dev"])
         lib().zscrc_set_opt(opt)
         try:
             with torch.cuda.device(m["dev"]):
@@ -200,7 +189,7 @@ def test_seeded_verdict_fenced(case, opt):
             torch.cuda.synchronize()
         finally:
             lib().zscrc_set_opt(0)
-        assert _intact(nw, 8) and _intact(bw, 8 * cap) and _intact(m["img_whole"], m["size"])
+        assert dm.intact(nw, 8) and dm.intact(bw, 8 * cap) and dm.intact(m["img_whole"], m["size"])
         k = int(nbad.cpu().view(torch.int64).item())
         listed = set(bad.cpu().view(torch.int64)[:min(k, cap)].tolist())
         assert k == len(want) and listed <= want and len(listed) == min(k, cap)
@@ -216,10 +205,10 @@ def test_writer_fenced(case, opt):
     m = case
     n = m["n"]
     rec, want, blank, crcs = m["has_rec"], m["w_image"], m["w_blank"], m["w_crc"]
-    iw, img = _fenced(blank.nbytes, m["dev"])
+    iw, img = dm.fenced(blank.nbytes, m["dev"])
     img.copy_(torch.from_numpy(blank))
-    cw, crc = _fenced(4 * n, m["dev"])
-    sw, st = _fenced(4 * n, m["dev"])
+    cw, crc = dm.fenced(4 * n, m["dev"])
+    sw, st = dm.fenced(4 * n, m["dev"])
     lib().zscrc_set_opt(opt)
     try:
         with torch.cuda.device(m["dev"]):
@@ -229,7 +218,7 @@ def test_writer_fenced(case, opt):
         torch.cuda.synchronize()
     finally:
         lib().zscrc_set_opt(0)
-    assert _intact(iw, blank.nbytes) and _intact(cw, 4 * n) and _intact(sw, 4 * n)
+    assert dm.intact(iw, blank.nbytes) and dm.intact(cw, 4 * n) and dm.intact(sw, 4 * n)
     assert np.array_equal(img.cpu().numpy(), want)
     got_st = st.cpu().numpy().view(np.int32)
     assert np.array_equal(got_st, np.where(rec, 1, 2))
@@ -243,8 +232,8 @@ def test_crc_array_fenced(case, opt):
     m = case
     n = m["n"]
     for with_status in (True, False):
-        cw, crc = _fenced(4 * n, m["dev"])
-        sw, st = _fenced(4 * n, m["dev"])
+        cw, crc = dm.fenced(4 * n, m["dev"])
+        sw, st = dm.fenced(4 * n, m["dev"])
         lib().zscrc_set_opt(opt)
         try:
             with torch.cuda.device(m["dev"]):
@@ -254,9 +243,9 @@ def test_crc_array_fenced(case, opt):
             torch.cuda.synchronize()
         finally:
             lib().zscrc_set_opt(0)
-        assert _intact(cw, 4 * n) and _intact(m["img_whole"], m["size"])
+        assert dm.intact(cw, 4 * n) and dm.intact(m["img_whole"], m["size"])
         if with_status:
-            assert _intact(sw, 4 * n)
+            assert dm.intact(sw, 4 * n)
             assert np.array_equal(st.cpu().numpy().view(np.int32), np.where(m["has_rec"], 1, 2))
         else:
             assert (sw.cpu().numpy() == CANARY).all()

@@ -13,62 +13,42 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import log_cases as lc
 from tests import pack_cases as pc
 from tests import records_images as ri
-from tests.test_log_host import check_against_image
+from tests.devmem import CANARY
+from tests.log_cases import check_against_image
 from zeroskip_amd import repack, zsfile
 from zeroskip_amd._lib import check, lib
 
 pytestmark = pytest.mark.gpu
 
-CANARY = 0xA5
-PAD = 4096
 TILES = [64, 4096, 0]
 TILE_IDS = ["t64", "t4096", "default"]
 WORDS = ("code", "n", "end", "written", "commits", "long_commits", "last_crc", "stored_crc")
-
-
-def _dev_bytes(b: bytes, dev, shift: int = 0) -> torch.Tensor:
-    """The bytes in device memory at an address = shift mod 16 (an empty tensor for none)."""
-    buf = torch.zeros(len(b) + 32, dtype=torch.uint8, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    d = buf[shift:shift + len(b)]
-    if len(b):
-        d.copy_(torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()))
-    return d
-
-
-def _dev_recs(recs: np.ndarray, dev) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(recs).view(np.int64).reshape(-1, 4).copy()).to(dev)
 
 
 def _dev_tx(case, dev):
     return None if case.tx_end is None else torch.tensor(case.tx_end, dtype=torch.int64, device=dev)
 
 
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
-
-
 def run_dev(case, dev, cap, tile=0, shift=0, scratch=None):
     """device_log of the case into `cap` canary bytes between fences, the prefix
     in place: (result dict with host copies, the cap bytes)."""
-    whole, out = _fenced(cap, dev)
+    whole, out = dm.fenced(cap, dev)
     assert out.data_ptr() % 16 == 0
     if case.at and cap >= case.at:
         out[:case.at].copy_(torch.from_numpy(np.frombuffer(case.prefix, np.uint8).copy()))
-    d_src = out[:case.at] if case.src_in_prefix else _dev_bytes(case.src, dev, shift)
-    d = zsfile.device_log(d_src, _dev_recs(case.recs, dev), _dev_tx(case, dev), case.uuid, case.startidx,
+    d_src = out[:case.at] if case.src_in_prefix else dm.dev_bytes(case.src, dev, shift)
+    d = zsfile.device_log(d_src, dm.dev_recs(case.recs, dev), _dev_tx(case, dev), case.uuid, case.startidx,
                           case.endidx, out=out, at=case.at, finalise=case.finalise, prev_crc=case.prev_crc,
                           tile_bytes=tile, new_recs=True, spans=True, scratch=scratch)
-    h = whole.cpu().numpy()
-    assert bool((h[:PAD] == CANARY).all() and (h[PAD + cap:] == CANARY).all()), case.name
+    got = dm.inside(whole, cap, case.name)
     for k in ("new_recs", "span_off", "span_len"):
         if d[k] is not None:
             d[k] = d[k].cpu().numpy().view(np.uint64)
-    return d, h[PAD:PAD + cap]
+    return d, got
 
 
 def same(case, dev, tile=0, shift=0, slack=64, scratch=None):
@@ -133,7 +113,7 @@ def test_exact_capacity_and_sized_by_the_wrapper(gpu):
         same(case, gpu, slack=0)                                          # out_cap == the end offset
         if case.at:
             continue
-        d = zsfile.device_log(_dev_bytes(case.src, gpu), _dev_recs(case.recs, gpu), _dev_tx(case, gpu), case.uuid,
+        d = zsfile.device_log(dm.dev_bytes(case.src, gpu), dm.dev_recs(case.recs, gpu), _dev_tx(case, gpu), case.uuid,
                               case.startidx, case.endidx, finalise=case.finalise)       # out=None
         assert d["code"] == 0 and d["image"].cpu().numpy().tobytes() == case.want, case.name
 
@@ -144,13 +124,13 @@ def test_bad_inputs_leave_everything_untouched(gpu, tile):
     base, bad = lc.bad_inputs()
     for name, case, cap, head in bad:
         cap = len(base.want) + 64 if cap is None else cap
-        whole, out = _fenced(cap, gpu)
+        whole, out = dm.fenced(cap, gpu)
         nr = torch.full((case.n, 4), 0x5A5A, dtype=torch.int64, device=gpu)
         so = torch.full((8,), 0x5A5A, dtype=torch.int64, device=gpu)
         sl = torch.full((8,), 0x5A5A, dtype=torch.int64, device=gpu)
         res = torch.full((8,), 0x77, dtype=torch.int64, device=gpu)
         te = torch.tensor(case.tx_end, dtype=torch.int64, device=gpu)
-        d_src, d_recs = _dev_bytes(case.src, gpu), _dev_recs(case.recs, gpu)
+        d_src, d_recs = dm.dev_bytes(case.src, gpu), dm.dev_recs(case.recs, gpu)
         opts = zsfile.LogOpts(tile, 0)
         check(lib().zscrc_device_log(d_src.data_ptr(), d_src.numel(), d_recs.data_ptr(), case.n,
                                      te.data_ptr() if te.numel() else res.data_ptr(), te.numel(), case.uuid, 3, 3,
@@ -173,7 +153,7 @@ def test_lister_and_verifier_agree(gpu):
     assert len(cases) == len(names)
     for case in cases:
         d, got = same(case, gpu)
-        img = _dev_bytes(case.want, gpu)
+        img = dm.dev_bytes(case.want, gpu)
         img.copy_(torch.from_numpy(got[:len(case.want)].copy()))
         recs, res = zsfile.device_records(img, zsfile.ACTIVE)
         lr = res.cpu().numpy().view(np.uint64)
@@ -213,9 +193,9 @@ def test_log_append_list_merge_pack(gpu):
     ca, cb = pc.from_pairs("A", a, seed=1), pc.from_pairs("B", b, seed=2)
     cap = 1 << 20
     out = torch.full((cap,), CANARY, dtype=torch.uint8, device=gpu)
-    da = zsfile.device_log(_dev_bytes(ca.src, gpu), _dev_recs(ca.recs, gpu), None, lc.UUID, 5, 5, out=out)
+    da = zsfile.device_log(dm.dev_bytes(ca.src, gpu), dm.dev_recs(ca.recs, gpu), None, lc.UUID, 5, 5, out=out)
     ends = torch.tensor(list(range(7, len(b), 7)) + [len(b)], dtype=torch.int64, device=gpu)
-    db = zsfile.device_log(_dev_bytes(cb.src, gpu, 3), _dev_recs(cb.recs, gpu), ends, out=out, at=da["end"], finalise=True)
+    db = zsfile.device_log(dm.dev_bytes(cb.src, gpu, 3), dm.dev_recs(cb.recs, gpu), ends, out=out, at=da["end"], finalise=True)
     assert da["code"] == 0 and db["code"] == 0 and db["end"] > da["end"]
     img = db["image"]
     recs, res = zsfile.device_records(img, zsfile.ACTIVE)
@@ -254,7 +234,7 @@ def test_seeded_soak(gpu):
         scratch = None
         if it % 2:
             need = zsfile.device_log_scratch_bytes(n, n if ends is None else len(ends), tile)
-            whole, scratch = _fenced(need, gpu)
+            whole, scratch = dm.fenced(need, gpu)
         torch.cuda.synchronize(gpu)
         if it % 4 < 2:
             with torch.cuda.stream(side):
@@ -262,8 +242,7 @@ def test_seeded_soak(gpu):
         else:
             same(case, gpu, tile=tile, shift=it % 8, scratch=scratch)
         if scratch is not None:
-            h = whole.cpu().numpy()
-            assert bool((h[:PAD] == CANARY).all() and (h[PAD + need:] == CANARY).all()), it
+            assert dm.intact(whole, need), it
 
 
 # ---------------------------------------------------------------- beyond 4 GiB
@@ -299,7 +278,7 @@ def test_offsets_beyond_4gib(gpu):
     big[:, 0] += np.uint64(B32)
     big[big[:, 2] != lc.U64_MAX, 2] += np.uint64(B32)
     assert int(big[:, 0].min()) >= B32
-    d = zsfile.device_log(d_src, _dev_recs(big, gpu), torch.tensor(ends, dtype=torch.int64, device=gpu), out=d_out,
+    d = zsfile.device_log(d_src, dm.dev_recs(big, gpu), torch.tensor(ends, dtype=torch.int64, device=gpu), out=d_out,
                           at=at, finalise=True, prev_crc=7, new_recs=True, spans=True)
     shift = at - at_h
     assert d["code"] == 0 and d["end"] == h["end"] + shift and d["written"] == h["written"]

@@ -16,7 +16,7 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
-from tests.test_format_oracle import UUID
+from tests.images import UUID
 from zeroskip_amd import zsfile
 from zeroskip_amd._lib import lib
 

@@ -9,51 +9,26 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import merge_cases as mc
+from tests.devmem import CANARY
+from tests.images import EINVAL64, OVERFLOW, U64_MAX, UUID, UUIDSTR
 from zeroskip_amd import repack, zsfile
 
 pytestmark = pytest.mark.gpu
 
-U64_MAX = (1 << 64) - 1
-CANARY = 0xA5
-PAD = 4096
-EINVAL64 = U64_MAX  # (uint64_t)(int64_t)ZSCRC_EINVAL
-OVERFLOW = 3
 TILES = [64, 256, 0]
 TILE_IDS = ["t64", "t256", "default"]
-UUID = bytes(range(16))
-UUIDSTR = "00010203-0405-0607-0809-0a0b0c0d0e0f"
-
-
-def _dev_bytes(b: bytes, dev, shift: int = 0) -> torch.Tensor:
-    """The bytes in device memory at an address = shift mod 16 (an empty tensor for none)."""
-    buf = torch.zeros(len(b) + 32, dtype=torch.uint8, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    d = buf[shift:shift + len(b)]
-    if len(b):
-        d.copy_(torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()))
-    return d
-
-
-def _dev_recs(recs: np.ndarray, dev) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(recs).view(np.int64).reshape(-1, 4).copy()).to(dev)
-
-
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
 
 
 def _merge(case, dev, drop, cap, tile=0, shift=0, scratch=None, dev_in=None):
     """device_merge into `cap` canary rows between fences: (the rows uint64 [cap, 4], res uint64[8])."""
-    d_src, lists = dev_in or (_dev_bytes(case.src, dev, shift), [(_dev_recs(r, dev), b) for r, b in case.lists])
-    whole, out = _fenced(32 * cap, dev)
+    d_src, lists = dev_in or (dm.dev_bytes(case.src, dev, shift), [(dm.dev_recs(r, dev), b) for r, b in case.lists])
+    whole, out = dm.fenced(32 * cap, dev)
     _, res = repack.device_merge(d_src, lists, drop_deletes=drop, out=out.view(torch.int64).view(cap, 4),
                                  tile_records=tile, scratch=scratch)
     r = res.cpu().numpy().view(np.uint64)
-    h = whole.cpu().numpy()
-    assert bool((h[:PAD] == CANARY).all() and (h[PAD + 32 * cap:] == CANARY).all()), case.name
-    return h[PAD:PAD + 32 * cap].view(np.uint64).reshape(cap, 4), r
+    return dm.inside(whole, 32 * cap, case.name).view(np.uint64).reshape(cap, 4), r
 
 
 def _same(case, dev, drop=False, tile=0, shift=0, slack=3, scratch=None, dev_in=None):
@@ -211,7 +186,7 @@ def test_capacity(gpu, cases):
             assert [int(v) for v in r] == [OVERFLOW] + wres[1:], (name, cap, r)
             assert got.tolist() == want[:cap].tolist(), (name, cap)
         # the sizing call: no output at all, then the wrapper's own
-        d_src, lists = _dev_bytes(c.src, gpu), [(_dev_recs(r, gpu), b) for r, b in c.lists]
+        d_src, lists = dm.dev_bytes(c.src, gpu), [(dm.dev_recs(r, gpu), b) for r, b in c.lists]
         _, res = repack.device_merge(d_src, lists, drop_deletes=drop, out=torch.empty((0, 4), dtype=torch.int64,
                                                                                        device=gpu))
         assert [int(v) for v in res.cpu().numpy()] == [OVERFLOW] + wres[1:]
@@ -226,18 +201,17 @@ def test_caller_scratch_fenced(gpu, cases):
         c = cases[name]
         need = repack.device_merge_scratch_bytes(c.n, tile)
         assert need > 0
-        whole, scratch = _fenced(need, gpu)
+        whole, scratch = dm.fenced(need, gpu)
         assert scratch.data_ptr() % 16 == 0
         _same(c, gpu, tile=tile, scratch=scratch)
-        h = whole.cpu().numpy()
-        assert bool((h[:PAD] == CANARY).all() and (h[PAD + need:] == CANARY).all()), name
+        assert dm.intact(whole, need), name
 
 
 def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     """A walk and a merge on two streams share the library's scratch, ordered by its event."""
     from tests import records_images as ri
     img = ri.wellformed()
-    d_img = _dev_bytes(img, gpu)
+    d_img = dm.dev_bytes(img, gpu)
     def walk():
         off, ln, res = zsfile.device_walk(d_img)
         return off, ln, res
@@ -249,7 +223,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     want_walk = listed(walk())
     assert want_walk[2][1] > 0
     c = cases["n1280"]
-    dev_in = (_dev_bytes(c.src, gpu), [(_dev_recs(r, gpu), b) for r, b in c.lists])
+    dev_in = (dm.dev_bytes(c.src, gpu), [(dm.dev_recs(r, gpu), b) for r, b in c.lists])
     s1, s2 = torch.cuda.Stream(device=gpu), torch.cuda.Stream(device=gpu)
     torch.cuda.synchronize(gpu)
     want, wres = c.model(False)
@@ -268,7 +242,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
 def test_two_runs_bit_for_bit(gpu, cases):
     for name, tile in (("n1280", 64), ("key_lengths", 0)):
         c = cases[name]
-        dev_in = (_dev_bytes(c.src, gpu), [(_dev_recs(r, gpu), b) for r, b in c.lists])
+        dev_in = (dm.dev_bytes(c.src, gpu), [(dm.dev_recs(r, gpu), b) for r, b in c.lists])
         a = _merge(c, gpu, False, c.n, tile, dev_in=dev_in)
         b = _merge(c, gpu, False, c.n, tile, dev_in=dev_in)
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
@@ -301,7 +275,7 @@ def test_more_blocks_than_one_scan_chunk(gpu):
         assert len(want) == n_out
         if order is not perm:                                  # as listed: the odd i and the last record
             assert np.array_equal(want, recs[np.r_[1:n:2, n - 1]])
-        out, res = repack.device_merge(d_src, [(_dev_recs(listed, gpu), 0)],
+        out, res = repack.device_merge(d_src, [(dm.dev_recs(listed, gpu), 0)],
                                        out=torch.zeros((n, 4), dtype=torch.int64, device=gpu))
         assert [int(v) for v in res.cpu().numpy().view(np.uint64)] == wres
         assert np.array_equal(out.cpu().numpy().view(np.uint64)[:n_out], want)
@@ -312,7 +286,7 @@ def test_more_blocks_than_one_scan_chunk(gpu):
 def test_random(gpu, seed):
     c = mc.random_case(seed)
     assert c.n == 2000 and 1 <= len(c.lists) <= 4
-    dev_in = (_dev_bytes(c.src, gpu), [(_dev_recs(r, gpu), b) for r, b in c.lists])
+    dev_in = (dm.dev_bytes(c.src, gpu), [(dm.dev_recs(r, gpu), b) for r, b in c.lists])
     for drop in (False, True):
         _same(c, gpu, drop, tile=(64, 256, 0)[seed % 3], dev_in=dev_in)
 
@@ -325,7 +299,7 @@ def _arena(images, dev):
         buf += bytes(-len(buf) % 64)
         at.append((len(buf), len(img)))
         buf += img
-    return _dev_bytes(bytes(buf), dev), at
+    return dm.dev_bytes(bytes(buf), dev), at
 
 
 def _finalised_images():

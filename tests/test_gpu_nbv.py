@@ -24,7 +24,8 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
-from tests.test_format_oracle import UUID
+from tests.images import UUID
+from tests.images import oracle_bad as _oracle_bad
 from zeroskip_amd import zsfile
 from zeroskip_amd._lib import DEFAULT_TEAMS, lib, stats
 
@@ -68,25 +69,6 @@ def _verdict(opt, d, o, ln, lo, hi, seed=None, cap=8192):
         lib().zscrc_set_opt(0)
     n = int(nbad.item())
     return n, set(bad[:min(n, cap)].cpu().tolist()), launches
-
-
-def _oracle_bad(img, offs, lens, cs_by_off, seeds=None):
-    """indices whose commit does not verify (outside the image: no commit)"""
-    hb = img.tobytes()
-    want = set()
-    for i, (o, n) in enumerate(zip(offs, lens)):
-        o, n = int(o), int(n)
-        if o > len(hb) or n > len(hb) - o or len(hb) - o - n < 8:
-            want.add(i)
-            continue
-        try:
-            _, _, _, stored, comp = zf._commit_check(hb, o + n, 0 if seeds is None else int(seeds[i]))
-        except ValueError:
-            want.add(i)
-            continue
-        if stored != comp:
-            want.add(i)
-    return want
 
 
 @pytest.fixture

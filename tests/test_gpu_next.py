@@ -10,74 +10,35 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import find_cases as fc
 from tests import next_cases as nc
+from tests.images import REF, U64_MAX, UUIDSTR
 from zeroskip_amd import repack, zsfile
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "tests", "golden", "ref_format")
-UUIDSTR = "00010203-0405-0607-0809-0a0b0c0d0e0f"
-U64_MAX = nc.U64_MAX
 U64 = np.uint64
-CANARY = 0xA5
-PAD = 4096
 SPLITS = [1, 2, 1024, 2048]      # no table, the smallest, the default, the largest
 PLAIN = (1, False, False, 0)
-
-
-def _dev_bytes(b: bytes, dev, shift: int = 0) -> torch.Tensor:
-    """The bytes in device memory at an address = shift mod 16 (an empty tensor for none)."""
-    buf = torch.zeros(len(b) + 32, dtype=torch.uint8, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    d = buf[shift:shift + len(b)]
-    if len(b):
-        d.copy_(torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()))
-    return d
-
-
-def _dev_recs(recs: np.ndarray, dev) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(recs).view(np.int64).reshape(-1, 4).copy()).to(dev)
-
-
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
-
-
-def _inside(whole, nbytes):
-    """The bytes between the fences, which must hold."""
-    h = whole.cpu().numpy()
-    assert bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all())
-    return h[PAD:PAD + nbytes]
-
-
-def _dev_in(case, dev, shift=0, qshift=0):
-    return (_dev_bytes(case.src, dev, shift), [(_dev_recs(r, dev), b) for r, b in case.levels],
-            _dev_bytes(case.qsrc, dev, qshift), _dev_recs(case.queries, dev))
 
 
 def _next(case, dev, setting=PLAIN, splitters=0, check_order=False, scratch=None, dev_in=None):
     """device_next into canary buffers between fences: (rows bytes [32 nq
     page], seqs bytes [8 nq page], cur bytes [32 nq], res uint64 [12])."""
     page, inclusive, keep, max_steps = setting
-    d_src, levels, d_qsrc, queries = dev_in or _dev_in(case, dev)
+    d_src, levels, d_qsrc, queries = dev_in or dm.dev_in(case, dev)
     nq = int(queries.shape[0])
-    wr, rows = _fenced(32 * nq * page, dev)
-    ws, seqs = _fenced(8 * nq * page, dev)
-    wc, cur = _fenced(32 * nq, dev)
+    wr, rows = dm.fenced(32 * nq * page, dev)
+    ws, seqs = dm.fenced(8 * nq * page, dev)
+    wc, cur = dm.fenced(32 * nq, dev)
     res = torch.full((zsfile.NEXT_RES_WORDS,), -6, dtype=torch.int64, device=dev)
     zsfile.device_next(d_src, levels, d_qsrc, queries, page=page, inclusive=inclusive, keep_deletes=keep,
                        check_order=check_order, max_steps=max_steps, splitters=splitters,
                        out=(rows.view(torch.int64).view(nq, page, 4), seqs.view(torch.int64).view(nq, page),
                             cur.view(torch.int64).view(nq, 4), res), scratch=scratch)
-    return (_inside(wr, 32 * nq * page), _inside(ws, 8 * nq * page), _inside(wc, 32 * nq),
+    return (dm.inside(wr, 32 * nq * page), dm.inside(ws, 8 * nq * page), dm.inside(wc, 32 * nq),
             [int(v) for v in res.cpu().numpy().view(U64)])
-
-
-def _all_canary(*arrays):
-    return all(bool((a == CANARY).all()) for a in arrays)
 
 
 def _b(a) -> bytes:
@@ -102,7 +63,7 @@ def _host(case, setting, check_order=False):
 def _same(case, dev, settings, splits=(0,), check_order=False, shift=0, qshift=0, host=True):
     """The case at every setting and table size: equal byte for byte to the
     model, and the model to the host form."""
-    dev_in = _dev_in(case, dev, shift, qshift)
+    dev_in = dm.dev_in(case, dev, shift, qshift)
     for setting in settings:
         want = case.model(*setting)
         if host:
@@ -152,7 +113,7 @@ def test_one_query_more_than_the_bounds_grid_has_threads(gpu):
     want = _host(case, PLAIN)
     assert want[3][0] == 0 and want[3][2] > nq // 2 and want[3][5] > 0 and want[3][4] > 0
     assert int(want[2][-1, 2]) == 1                 # the query of the second trip has its row
-    dev_in = _dev_in(case, gpu)
+    dev_in = dm.dev_in(case, gpu)
     for s in (0, 1):
         _equal(_next(case, gpu, PLAIN, s, dev_in=dev_in), want, ("grid", s))
 
@@ -190,27 +151,27 @@ def test_random_cases(gpu):
 # ---------------------------------------------------------------------- refusals
 def test_a_record_outside_the_source(gpu):
     case, seq = nc.bad_record_case()
-    dev_in = _dev_in(case, gpu)
+    dev_in = dm.dev_in(case, gpu)
     for s in SPLITS:
         for check_order in (False, True):
             rows, seqs, cur, res = _next(case, gpu, (2, False, False, 0), s, check_order, dev_in=dev_in)
             assert res == [nc.EINVAL64, seq] + [0] * 10
-            assert _all_canary(rows, seqs, cur)
+            assert dm.all_canary(rows, seqs, cur)
 
 
 def test_check_order(gpu):
     case = nc.unordered_case()
-    dev_in = _dev_in(case, gpu)
+    dev_in = dm.dev_in(case, gpu)
     for s in SPLITS:
         rows, seqs, cur, res = _next(case, gpu, (2, True, False, 0), s, True, dev_in=dev_in)
         assert res == [nc.EINVAL64, 2] + [0] * 5 + [1] + [0] * 4
-        assert _all_canary(rows, seqs, cur)
+        assert dm.all_canary(rows, seqs, cur)
     # a bounds offence goes before an order offence at a smaller seq
     recs = case.levels[0][0].copy()
     recs[6, 1] = len(case.src)
     both = nc.NextCase("both", case.src, [(recs, 0), case.levels[1]], case.qsrc, case.queries)
     rows, seqs, cur, res = _next(both, gpu, PLAIN, 0, True)
-    assert res == [nc.EINVAL64, 6] + [0] * 10 and _all_canary(rows, seqs, cur)
+    assert res == [nc.EINVAL64, 6] + [0] * 10 and dm.all_canary(rows, seqs, cur)
 
 
 def test_a_level_that_does_not_ascend_stays_inside_its_buffers(gpu):
@@ -218,17 +179,17 @@ def test_a_level_that_does_not_ascend_stays_inside_its_buffers(gpu):
     and of the scratch hold, the code is 0 and no query takes more steps than
     there are records."""
     for case in (nc.unordered_case(), nc.shuffled_case(0)):
-        dev_in = _dev_in(case, gpu)
+        dev_in = dm.dev_in(case, gpu)
         nq = len(case.queries)
         for s in SPLITS:
             for setting in ((1, False, False, 0), (64, True, True, 0)):
                 need = zsfile.device_next_scratch_bytes(nq, len(case.levels), s)
-                whole, scratch = _fenced(need, gpu)
+                whole, scratch = dm.fenced(need, gpu)
                 rows, seqs, cur, res = _next(case, gpu, setting, s, scratch=scratch, dev_in=dev_in)
                 cur = cur.view(U64).reshape(-1, 4)
                 assert res[0] == 0 and res[1] == nq and res[3] <= case.n * nq and int(cur[:, 2].sum()) == res[2]
                 assert int(cur[:, 2].max()) <= setting[0] and set(cur[:, 3].tolist()) <= {nc.PAGE, nc.END}
-                _inside(whole, need)
+                dm.inside(whole, need)
 
 
 # --------------------------------------------- scratch, streams and determinism
@@ -239,16 +200,16 @@ def test_caller_scratch_fenced(gpu, cases):
         setting = (3, True, False, 0)
         need = zsfile.device_next_scratch_bytes(len(c.queries), len(c.levels), s)
         assert need > 0
-        whole, scratch = _fenced(need, gpu)
+        whole, scratch = dm.fenced(need, gpu)
         assert scratch.data_ptr() % 16 == 0
         _equal(_next(c, gpu, setting, s, scratch=scratch), c.model(*setting), name)
-        _inside(whole, need)
+        dm.inside(whole, need)
 
 
 def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     """A walk and a call of the stage on two streams share the library's scratch, ordered by its event."""
     from tests import records_images as ri
-    d_img = _dev_bytes(ri.wellformed(), gpu)
+    d_img = dm.dev_bytes(ri.wellformed(), gpu)
 
     def listed(walked):
         off, ln, res = (t.cpu().numpy() for t in walked)
@@ -257,7 +218,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     want_walk = listed(zsfile.device_walk(d_img))
     assert want_walk[2][1] > 0
     c = cases["n65"]
-    dev_in = _dev_in(c, gpu)
+    dev_in = dm.dev_in(c, gpu)
     wrows, wseqs, wcur, wres = c.model(3, False, False, 0)
     s1, s2 = torch.cuda.Stream(device=gpu), torch.cuda.Stream(device=gpu)
     torch.cuda.synchronize(gpu)
@@ -275,7 +236,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
 
 def test_two_runs_bit_for_bit(gpu, cases):
     for c, s in ((cases["n65"], 64), (cases["many_levels"], 0), (nc.random_case(1), 2)):
-        dev_in = _dev_in(c, gpu)
+        dev_in = dm.dev_in(c, gpu)
         setting = (7, False, True, 3)
         a = _next(c, gpu, setting, s, dev_in=dev_in)
         b = _next(c, gpu, setting, s, dev_in=dev_in)
@@ -290,7 +251,7 @@ def _dev_chain(d_src, levels, dev, page, keep, max_steps=0, check_order=False):
     calls, MOREs seen) once the chain is over."""
     qsrc, queries = fc.lay_queries([b""])
     parts, mores = [], 0
-    rows, seq, cur, res = zsfile.device_next(d_src, levels, _dev_bytes(qsrc, dev), _dev_recs(queries, dev), page=page,
+    rows, seq, cur, res = zsfile.device_next(d_src, levels, dm.dev_bytes(qsrc, dev), dm.dev_recs(queries, dev), page=page,
                                              inclusive=True, keep_deletes=keep, max_steps=max_steps,
                                              check_order=check_order)
     while True:
@@ -312,8 +273,8 @@ def _dev_chain(d_src, levels, dev, page, keep, max_steps=0, check_order=False):
 
 def _chain_is_the_scan(src, levels, dev, pages=(1, 7, 64), steps=(0, 3)):
     qsrc, queries = fc.lay_queries([b""])
-    d_src = _dev_bytes(src, dev)
-    d_levels = [(_dev_recs(r, dev), b) for r, b in levels]
+    d_src = dm.dev_bytes(src, dev)
+    d_levels = [(dm.dev_recs(r, dev), b) for r, b in levels]
     for keep in (False, True):
         want = zsfile.scan(src, levels, qsrc, queries, keep_deletes=keep)
         assert int(want[3][0]) == 0
@@ -329,7 +290,7 @@ def test_a_chained_pages_are_the_empty_prefix_scan(gpu, cases):
     _chain_is_the_scan(cases["many_levels"].src, cases["many_levels"].levels, gpu, pages=(7, 64))
     c = cases["run65"]
     _chain_is_the_scan(c.src, c.levels, gpu, pages=(1, 64))
-    d_in = _dev_in(c, gpu)
+    d_in = dm.dev_in(c, gpu)
     assert _dev_chain(d_in[0], d_in[1], gpu, 64, False, 3)[3] > 10      # MORE occurs, and the chain goes through it
     c = nc.random_case(1)
     _chain_is_the_scan(c.src, c.levels, gpu, pages=(64,), steps=(0, 50))
@@ -339,7 +300,7 @@ def test_b_one_level_is_the_lookup_s_location_plus_found(gpu):
     src, recs = fc.counted_level(194)
     recs = recs[recs[:, 2] != U64_MAX]                            # no deletes
     c = nc.over("live", src, [(recs, 0)])
-    dev_in = _dev_in(c, gpu)
+    dev_in = dm.dev_in(c, gpu)
     hits, fres = zsfile.device_find(*dev_in)
     rows, seq, cur, res = zsfile.device_next(*dev_in)
     hits, rows, seq, cur = (t.cpu().numpy().view(U64) for t in (hits, rows, seq, cur))
@@ -354,7 +315,7 @@ def test_b_one_level_is_the_lookup_s_location_plus_found(gpu):
 
 def test_c_every_row_is_where_its_seq_says(gpu, cases):
     for c in [cases[n] for n in ("many_levels", "winners", "five_levels", "shared_prefix")] + [nc.random_case(2)]:
-        d_src, levels, d_qsrc, queries = _dev_in(c, gpu)
+        d_src, levels, d_qsrc, queries = dm.dev_in(c, gpu)
         rows, seq, cur, res = zsfile.device_next(d_src, levels, d_qsrc, queries, page=3, keep_deletes=True)
         live = rows[:, :, 0] != zsfile.FIND_NONE
         hits, fres = zsfile.device_find(d_src, levels, d_src, rows[live].contiguous())
@@ -382,8 +343,8 @@ def test_d_reference_repack_inputs(gpu, name):
         assert rc == 0
         levels.append((np.ascontiguousarray(recs.T), off))
     _chain_is_the_scan(arena, levels, gpu, pages=(7, 64), steps=(0,))
-    d_levels = [(_dev_recs(r, gpu), b) for r, b in levels]
-    rows, _, _, _ = _dev_chain(_dev_bytes(arena, gpu), d_levels, gpu, 64, False, check_order=True)
+    d_levels = [(dm.dev_recs(r, gpu), b) for r, b in levels]
+    rows, _, _, _ = _dev_chain(dm.dev_bytes(arena, gpu), d_levels, gpu, 64, False, check_order=True)
     got = [(arena[ko:ko + kl], arena[vo:vo + vl]) for ko, kl, vo, vl in rows.tolist()]
     assert got == zf.repack_packed(older, newer) and len(got) > 400
 
@@ -392,7 +353,7 @@ def test_d_reference_repack_inputs(gpu, name):
 def test_fetchnext_keys_and_values(gpu, cases):
     """device_fetchnext's two CSR pairs against the bytes the model's rows name."""
     for c, keep in ((cases["winners"], False), (cases["winners"], True), (nc.random_case(3), True)):
-        dev_in = _dev_in(c, gpu)
+        dev_in = dm.dev_in(c, gpu)
         wrows, wseqs, wcur, wres = c.model(3, True, keep, 0)
         keys, koffs, values, voffs, rows, seq, cur, nres, gres = zsfile.device_fetchnext(
             *dev_in, page=3, inclusive=True, keep_deletes=keep)
@@ -410,7 +371,7 @@ def test_fetchnext_keys_and_values(gpu, cases):
         assert int(gres[2]) == wres[2] - (wres[5] if keep else 0) and int(gres[5]) == sum(f[0] == nc.NONE for f in flat)
     # a refused call runs no gather
     bad, _ = nc.bad_record_case()
-    out = zsfile.device_fetchnext(*_dev_in(bad, gpu))
+    out = zsfile.device_fetchnext(*dm.dev_in(bad, gpu))
     assert int(out[7][0]) == -1 and out[0] is None and out[2] is None and out[8] is None
 
 
@@ -432,7 +393,7 @@ def test_offsets_beyond_4_gib(gpu, cases):
     d_src = torch.empty(size, dtype=torch.uint8, device=gpu)
     d_src[base:base + len(c.src)].copy_(torch.from_numpy(np.frombuffer(c.src, np.uint8).copy()))
     d_src[base + qat:base + qat + len(c.qsrc)].copy_(torch.from_numpy(np.frombuffer(c.qsrc, np.uint8).copy()))
-    levels = [(_dev_recs(r, gpu), base + b) for r, b in c.levels]
+    levels = [(dm.dev_recs(r, gpu), base + b) for r, b in c.levels]
     queries = c.queries.copy()
     queries[:, 0] += np.uint64(base + qat)
 
@@ -448,7 +409,7 @@ def test_offsets_beyond_4_gib(gpu, cases):
 
     setting = (3, False, True, 0)
     first = c.model(*setting)
-    rows, seq, cur, res = zsfile.device_next(d_src, levels, d_src, _dev_recs(queries, gpu), page=3, keep_deletes=True,
+    rows, seq, cur, res = zsfile.device_next(d_src, levels, d_src, dm.dev_recs(queries, gpu), page=3, keep_deletes=True,
                                              check_order=True)
     got = [t.cpu().numpy().view(U64) for t in (rows, seq, cur)] + [[int(v) for v in res.cpu().numpy().view(U64)]]
     _equal(got, shifted(first), "first page")

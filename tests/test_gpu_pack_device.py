@@ -8,38 +8,17 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import pack_cases as pc
 from tests import records_images as ri
+from tests.devmem import CANARY
+from tests.images import EINVAL64, OVERFLOW, U64_MAX
 from zeroskip_amd import repack, zsfile
 
 pytestmark = pytest.mark.gpu
 
-U64_MAX = (1 << 64) - 1
-CANARY = 0xA5
-PAD = 4096
-EINVAL64 = U64_MAX  # (uint64_t)(int64_t)ZSCRC_EINVAL
-OVERFLOW = 3
 TILES = [64, 128, 4096, 0]
 TILE_IDS = ["t64", "t128", "t4096", "default"]
-
-
-def _dev_bytes(b: bytes, dev, shift: int = 0) -> torch.Tensor:
-    """The bytes in device memory at an address = shift mod 16 (an empty tensor for none)."""
-    buf = torch.zeros(len(b) + 32, dtype=torch.uint8, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    d = buf[shift:shift + len(b)]
-    if len(b):
-        d.copy_(torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()))
-    return d
-
-
-def _dev_recs(recs: np.ndarray, dev) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(recs).view(np.int64).reshape(-1, 4).copy()).to(dev)
-
-
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
 
 
 def _bound(recs: np.ndarray) -> int:
@@ -52,20 +31,18 @@ def _bound(recs: np.ndarray) -> int:
 def _pack(d_src, d_recs, case, cap, tile=0, scratch=None):
     """device_pack into `cap` canary bytes between fences: (the cap bytes, res uint64[8])."""
     dev = d_src.device
-    whole, out = _fenced(cap, dev)
+    whole, out = dm.fenced(cap, dev)
     assert out.data_ptr() % 16 == 0
     _, res = repack.device_pack(d_src, d_recs, case.uuid, case.startidx, case.endidx, out=out, tile_bytes=tile,
                                 scratch=scratch)
     r = res.cpu().numpy().view(np.uint64)
-    h = whole.cpu().numpy()
-    assert bool((h[:PAD] == CANARY).all() and (h[PAD + cap:] == CANARY).all()), case.name
-    return h[PAD:PAD + cap], r
+    return dm.inside(whole, cap, case.name), r
 
 
 def _same(case, dev, want: bytes, tile=0, shift=0, slack=64, d_recs=None, d_src=None, scratch=None):
     """The case packed into len(want) + slack bytes equals want; returns res."""
-    d_src = _dev_bytes(case.src, dev, shift) if d_src is None else d_src
-    d_recs = _dev_recs(case.recs, dev) if d_recs is None else d_recs
+    d_src = dm.dev_bytes(case.src, dev, shift) if d_src is None else d_src
+    d_recs = dm.dev_recs(case.recs, dev) if d_recs is None else d_recs
     got, r = _pack(d_src, d_recs, case, len(want) + slack, tile, scratch)
     what = (case.name, tile, shift)
     assert [int(v) for v in r[:3]] == [0, len(case.recs), len(want)], (what, r)
@@ -105,7 +82,7 @@ def test_empty_and_single(gpu, cases, host_files):
 @pytest.mark.parametrize("tile", TILES, ids=TILE_IDS)
 def test_alignment_grid(gpu, cases, host_files, tile):
     c = cases["alignment_grid"]
-    d_recs = _dev_recs(c.recs, gpu)
+    d_recs = dm.dev_recs(c.recs, gpu)
     for shift in range(8):
         _same(c, gpu, host_files[c.name][1], tile=tile, shift=shift, d_recs=d_recs)
 
@@ -121,7 +98,7 @@ def test_tile_boundaries(gpu, cases, host_files):
 # -------------------------------------------------------------------- log order
 def test_log_order_without_leaving_the_device(gpu, cases, host_files):
     c = cases["log_order"]
-    d = _dev_bytes(c.src, gpu)
+    d = dm.dev_bytes(c.src, gpu)
     recs, res = zsfile.device_records(d, zsfile.ACTIVE)
     lr = res.cpu().numpy().view(np.uint64)
     n = int(lr[1])
@@ -140,7 +117,7 @@ def test_round_trips(gpu, cases, host_files):
     assert len(names) == 5
     for name in names:
         c = cases[name]
-        d = _dev_bytes(c.src, gpu)
+        d = dm.dev_bytes(c.src, gpu)
         recs, res = zsfile.device_records(d, zsfile.PACKED)
         lr = res.cpu().numpy().view(np.uint64)
         n = int(lr[1])
@@ -204,7 +181,7 @@ def test_capacity(gpu, cases, host_files):
     for name in ("log_order", "single_kv", "empty"):
         c, want = cases[name], host_files[name][1]
         region = host_files[name][0]["region_bytes"]
-        d_src, d_recs = _dev_bytes(c.src, gpu), _dev_recs(c.recs, gpu)
+        d_src, d_recs = dm.dev_bytes(c.src, gpu), dm.dev_recs(c.recs, gpu)
         _same(c, gpu, want, slack=0, d_src=d_src, d_recs=d_recs)          # out_cap == file_bytes
         for cap in (len(want) - 1, len(want) - 16, 48, 0):
             got, r = _pack(d_src, d_recs, c, cap)
@@ -221,14 +198,14 @@ def test_capacity(gpu, cases, host_files):
 def test_bad_records(gpu, cases, host_files):
     c = cases["log_order"]
     n, size = len(c.recs), len(c.src)
-    d_src = _dev_bytes(c.src, gpu)
+    d_src = dm.dev_bytes(c.src, gpu)
     live = int(np.flatnonzero(c.recs[:, 2] != U64_MAX)[5])
 
     def bad(changes, first):
         recs = c.recs.copy()
         for i, col, v in changes:
             recs[i, col] = v
-        got, r = _pack(d_src, _dev_recs(recs, gpu), c, len(c.want) + 64, tile=64)
+        got, r = _pack(d_src, dm.dev_recs(recs, gpu), c, len(c.want) + 64, tile=64)
         assert int(r[0]) == EINVAL64 and int(r[1]) == first, (changes, r)
         assert [int(v) for v in r[4:8]] == [0, 0, 0, 0]
         assert bool((got == CANARY).all()), changes
@@ -245,7 +222,7 @@ def test_bad_records(gpu, cases, host_files):
     recs = c.recs.copy()
     recs[3] = (size - 5, 5, size, 0)
     recs[4] = (size, 0, U64_MAX, 0)
-    got, r = _pack(d_src, _dev_recs(recs, gpu), c, len(c.want) + 4096, tile=64)
+    got, r = _pack(d_src, dm.dev_recs(recs, gpu), c, len(c.want) + 4096, tile=64)
     ok = pc.Case("edge", c.src, recs)
     assert int(r[0]) == 0 and got[:int(r[2])].tobytes() == ok.want
 
@@ -259,7 +236,7 @@ def test_result_words_and_verification(gpu, cases, host_files):
         assert [int(v) for v in r] == [0, rep["records"], rep["file_bytes"], rep["region_bytes"], rep["region_crc"],
                                        rep["pointers_crc"], rep["commit_crc"], rep["final_crc"]], name
     c = cases["log_order"]
-    img, _ = repack.device_pack(_dev_bytes(c.src, gpu), _dev_recs(c.recs, gpu), c.uuid, c.startidx, c.endidx)
+    img, _ = repack.device_pack(dm.dev_bytes(c.src, gpu), dm.dev_recs(c.recs, gpu), c.uuid, c.startidx, c.endidx)
     v = zsfile.verify_device_image(img, zsfile.PACKED)
     assert v["walk_rc"] == 0 and v["n_commits"] == 2 and v["n_bad"] == 0 and v["header_rc"] == 0
     assert v["header_stored"] == v["header_computed"]
@@ -276,19 +253,18 @@ def test_caller_scratch_fenced(gpu, cases, host_files):
         c = cases[name]
         need = repack.device_pack_scratch_bytes(len(c.recs), tile)
         assert need > 0
-        whole, scratch = _fenced(need, gpu)
+        whole, scratch = dm.fenced(need, gpu)
         assert scratch.data_ptr() % 16 == 0
         _same(c, gpu, host_files[name][1], tile=tile, scratch=scratch)
-        h = whole.cpu().numpy()
-        assert bool((h[:PAD] == CANARY).all() and (h[PAD + need:] == CANARY).all()), name
+        assert dm.intact(whole, need), name
 
 
 def test_library_scratch_from_two_streams(gpu, cases, host_files):
     """Two packs on two streams share the library's scratch, ordered by its event."""
     a, b = cases["log_order"], cases["alignment_grid"]
-    sa, ra, sb, rb = _dev_bytes(a.src, gpu), _dev_recs(a.recs, gpu), _dev_bytes(b.src, gpu), _dev_recs(b.recs, gpu)
-    wa, oa = _fenced(len(a.want) + 64, gpu)
-    wb, ob = _fenced(len(b.want) + 64, gpu)
+    sa, ra, sb, rb = dm.dev_bytes(a.src, gpu), dm.dev_recs(a.recs, gpu), dm.dev_bytes(b.src, gpu), dm.dev_recs(b.recs, gpu)
+    wa, oa = dm.fenced(len(a.want) + 64, gpu)
+    wb, ob = dm.fenced(len(b.want) + 64, gpu)
     s1, s2 = torch.cuda.Stream(device=gpu), torch.cuda.Stream(device=gpu)
     torch.cuda.synchronize(gpu)
     results = []
@@ -307,7 +283,7 @@ def test_library_scratch_from_two_streams(gpu, cases, host_files):
 def test_side_stream(gpu, cases, host_files):
     c = cases["tile_boundaries"]
     side = torch.cuda.Stream(device=gpu)
-    d_src, d_recs = _dev_bytes(c.src, gpu), _dev_recs(c.recs, gpu)
+    d_src, d_recs = dm.dev_bytes(c.src, gpu), dm.dev_recs(c.recs, gpu)
     torch.cuda.synchronize(gpu)
     with torch.cuda.stream(side):
         _same(c, gpu, host_files[c.name][1], tile=64, d_src=d_src, d_recs=d_recs)
@@ -316,7 +292,7 @@ def test_side_stream(gpu, cases, host_files):
 def test_two_runs_bit_for_bit(gpu, cases):
     for name, tile in (("log_order", 0), ("alignment_grid", 64)):
         c = cases[name]
-        d_src, d_recs = _dev_bytes(c.src, gpu), _dev_recs(c.recs, gpu)
+        d_src, d_recs = dm.dev_bytes(c.src, gpu), dm.dev_recs(c.recs, gpu)
         a = _pack(d_src, d_recs, c, len(c.want) + 64, tile)
         b = _pack(d_src, d_recs, c, len(c.want) + 64, tile)
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()

@@ -12,19 +12,17 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import fuzzlib
 from tests import records_images as ri
-from tests.test_format_oracle import UUID, build_active
-from tests.walk_images import boundary_cases, short_commit, unaligned_image, unaligned_tail_image
+from tests.images import U64_MAX, UUID, build_active
+from tests.walk_images import boundary_cases, unaligned_image, unaligned_tail_image
 from zeroskip_amd import zsfile
 
 pytestmark = pytest.mark.gpu
 
 A, F, P = zsfile.ACTIVE, zsfile.FINALISED, zsfile.PACKED
-U64_MAX = (1 << 64) - 1
-CANARY = 0xA5
 CANARY64 = 0xA5A5A5A5A5A5A5A5
-PAD = 4096
 RES = zsfile.RECORDS_RES_WORDS
 # (block_bytes, tile_bytes); 0 = the default; block == tile = 16384; one block for the whole image
 GEOMETRIES = [(0, 0), (64, 64), (512, 64), (4096, 512), (16384, 16384), (1 << 30, 16384)]
@@ -41,16 +39,6 @@ def _dev(img: bytes, dev, shift: int = 0) -> torch.Tensor:
     return d
 
 
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
-
-
-def _intact(whole: torch.Tensor, nbytes: int) -> bool:
-    h = whole.cpu().numpy()
-    return bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all())
-
-
 def _list(d, kind, cap=None, block=0, tile=0, serial=False, scratch=None):
     """device_records into canary-filled buffers between fences: (recs uint64
     [max(cap, 1), 4], res uint64 [RES])."""
@@ -58,23 +46,14 @@ def _list(d, kind, cap=None, block=0, tile=0, serial=False, scratch=None):
     if cap is None:
         cap = size // 24 + 1
     rows = max(cap, 1)
-    fr, recs = _fenced(rows * 32, d.device)
-    fs, res = _fenced(RES * 8, d.device)
+    fr, recs = dm.fenced(rows * 32, d.device)
+    fs, res = dm.fenced(RES * 8, d.device)
     zsfile.device_records(d, kind, cap=cap, block_bytes=block, tile_bytes=tile, serial=serial, scratch=scratch,
                           out=(recs.view(torch.int64).view(rows, 4), res.view(torch.int64)))
     r = res.cpu().numpy().view(np.uint64)
     out = recs.cpu().numpy().view(np.uint64).reshape(rows, 4)
-    assert _intact(fr, rows * 32) and _intact(fs, RES * 8)
+    assert dm.intact(fr, rows * 32) and dm.intact(fs, RES * 8)
     return out, r
-
-
-def _folds(h: np.ndarray):
-    """res[3..7] of a host record list."""
-    if len(h) == 0:
-        return [0, 0, 0, 0, 0]
-    with np.errstate(over="ignore"):
-        return [int((h[:, 2] == U64_MAX).sum()), int(h[:, 1].sum(dtype=np.uint64)), int(h[:, 3].sum(dtype=np.uint64)),
-                int(h[:, 1].max()), int(h[:, 3].max())]
 
 
 def _same(img: bytes, d, kind, host=None, cap=None, what=None, **kw):
@@ -88,7 +67,7 @@ def _same(img: bytes, d, kind, host=None, cap=None, what=None, **kw):
     assert int(r[0]) == (zsfile.OVERFLOW if n > full else hrc) and int(r[1]) == n, (what, r[:3], hrc, n)
     assert np.array_equal(got[:m], h[:m]), what
     assert bool((got[m:] == CANARY64).all()), what           # nothing stored past min(n, cap)
-    assert [int(v) for v in r[3:8]] == _folds(h), (what, r[3:8])
+    assert [int(v) for v in r[3:8]] == ri.folds(h), (what, r[3:8])
     assert [int(v) for v in r[9:12]] == [0, 0, 0], what
     end = int(r[2])
     if kind == P:
@@ -167,32 +146,13 @@ def test_disagreement_images(gpu, block, tile):
 
 
 # ------------------------------------------------------- unaligned continuation
-def unaligned_records_image(prefix: bytes):
-    """prefix + a key record of 4 key bytes whose value offset is 28 (its value
-    header right behind the key, at an offset = 4 mod 8) + a delete record, a
-    key / value record and a commit, all at offsets = 4 mod 8.  Returns (image,
-    the first unaligned offset, the records before the crafted one)."""
-    assert len(prefix) % 8 == 0
-    K = len(prefix)
-    rec = zf.be64((zf.REC_KEY << 56) | (4 << 40) | 28) + bytes(16) + b"key4" + \
-        zf.be64((zf.REC_VALUE << 56) | (5 << 32)) + zf.be64(0) + b"value" + bytes(3)
-    assert len(rec) == 52
-    tail = zf.delete_record(b"8bytekey") + zf.key_record(b"tail-key") + zf.value_record(b"t" * 13)
-    img = prefix + rec + tail + short_commit(len(tail))
-    before, _ = ri.host_records(prefix, A)
-    h, rc = ri.host_records(img, A)
-    assert rc == zsfile.END and len(h) == len(before) + 3 and (K + 52) % 8 == 4
-    assert [int(v) for v in h[len(before)]] == [K + 24, 4, K + 44, 5] and int(h[len(before) + 1][0]) == K + 52 + 24
-    return img, K + 52, len(before)
-
-
 @pytest.mark.parametrize("block,tile", GEOMETRIES[:4], ids=GEOMETRY_IDS[:4])
 def test_unaligned_continuation(gpu, wellformed, block, tile):
     """A value offset that is no multiple of 8 leads the lister to records at
     offsets = 4 mod 8: the one-lane loop takes over there (res[8]) and lists
     them, and its folds meet the emit launch's atomics in res[3..7]."""
     prefix, _ = wellformed
-    img, first, n0 = unaligned_records_image(prefix)
+    img, first, n0 = ri.unaligned_records_image(prefix)
     host = ri.host_records(img, A)
     d = _dev(img, gpu)
     r = _same(img, d, A, host, block=block, tile=tile)
@@ -273,7 +233,7 @@ def test_cap(gpu, wellformed):
                                                          torch.empty(RES, dtype=torch.int64, device=gpu)), **kw)
         r = res.cpu().numpy().view(np.uint64)
         assert (int(r[0]), int(r[1]), int(r[2])) == (zsfile.OVERFLOW, n, len(img))
-        assert [int(v) for v in r[3:8]] == _folds(host[0])
+        assert [int(v) for v in r[3:8]] == ri.folds(host[0])
 
 
 # -------------------------------------------------------------- device address
@@ -336,15 +296,15 @@ def test_caller_scratch_fenced(gpu, wellformed, block, tile):
     img, host = wellformed
     need = zsfile.records_scratch_bytes(len(img), A, block, tile)
     assert need > 0
-    whole, scratch = _fenced(need, gpu)
+    whole, scratch = dm.fenced(need, gpu)
     assert scratch.data_ptr() % 16 == 0
     _same(img, _dev(img, gpu), A, host, block=block, tile=tile, scratch=scratch)
-    assert _intact(whole, need)
+    assert dm.intact(whole, need)
     pimg, _ = ri.packed_small(60)
     need = zsfile.records_scratch_bytes(len(pimg), P)
-    whole, scratch = _fenced(need, gpu)
+    whole, scratch = dm.fenced(need, gpu)
     _same(pimg, _dev(pimg, gpu), P, scratch=scratch)
-    assert _intact(whole, need)
+    assert dm.intact(whole, need)
 
 
 def test_library_scratch_across_streams(gpu, wellformed):
@@ -366,7 +326,7 @@ def test_library_scratch_across_streams(gpu, wellformed):
     r = res.cpu().numpy().view(np.uint64)
     assert (int(r[0]), int(r[1]), int(r[2])) == (host[1], len(host[0]), len(img))
     assert np.array_equal(recs[:len(host[0])].cpu().numpy().view(np.uint64), host[0])
-    assert [int(v) for v in r[3:8]] == _folds(host[0])
+    assert [int(v) for v in r[3:8]] == ri.folds(host[0])
 
 
 def test_two_runs_bit_for_bit(gpu, wellformed):

@@ -16,20 +16,25 @@ import torch
 
 from oracle import zs_format as zf
 from tests import fuzzlib
+from tests import devmem as dm
 from tests import records_images as ri
 from tests import walk_images as wi
-from tests.test_format_oracle import UUID, build_active
-from tests.test_gpu_merge import UUIDSTR
-from tests.test_gpu_records import _folds, unaligned_records_image
-from tests.test_gpu_walk_multi import CANARY, CANARY_WORD, PAD, _arena, _canary, _finalised, _key70k, _stopped
+from tests.arena_cases import EINVAL_WORD
+from tests.arena_cases import arena as _arena
+from tests.arena_cases import finalised as _finalised
+from tests.arena_cases import key70k as _key70k
+from tests.arena_cases import records_check as _check
+from tests.arena_cases import records_expect as _expect
+from tests.arena_cases import records_run as _run
+from tests.arena_cases import stopped as _stopped
+from tests.images import U64_MAX, UUID, UUIDSTR, build_active
+from tests.records_images import folds as _folds
+from tests.records_images import unaligned_records_image
 from zeroskip_amd import repack, zsfile
 
 pytestmark = pytest.mark.gpu
 
 A = zsfile.ACTIVE
-ROW, TOT = zsfile.RECORDS_ROW_WORDS, zsfile.RECORDS_TOT_WORDS
-U64_MAX = (1 << 64) - 1
-EINVAL_WORD = U64_MAX                # (uint64_t)(int64_t)ZSCRC_EINVAL
 GEOMETRIES = [(64, 64), (512, 64), (4096, 512), (0, 0)]
 GEOMETRY_IDS = ["b64_t64", "b512_t64", "b4096_t512", "default"]
 
@@ -44,90 +49,6 @@ def _odd_gaps(images):
         gaps.append(gap)
         pos += gap + len(img)
     return gaps
-
-
-def _trajectory(img: bytes, h: np.ndarray, rc: int):
-    """(row word [2], row word [8]) of an image of 40 bytes and more from its
-    host list: the lister's offsets from 40 -- a listed record leads to the
-    end of its value (or of its key, a delete), a commit record is 8 or 24
-    bytes, anything else is where the lister ended -- and the first of them
-    that is no multiple of 8."""
-    size, off, i, take = len(img), 40, 0, U64_MAX
-    while off < size:
-        if off % 8 and take == U64_MAX:
-            take = off
-        if i < len(h) and int(h[i][0]) == off + 24:
-            _, klen, voff, vlen = (int(v) for v in h[i])
-            off = off + 24 + zf.rup8(klen) if voff == U64_MAX else voff + zf.rup8(vlen)
-            i += 1
-            continue
-        rl = {zf.REC_COMMIT: 8, zf.REC_LONG_COMMIT: 24}.get(img[off]) if size - off >= 8 else None
-        if rl is None or size - off < rl:
-            break
-        off += rl
-    assert i == len(h) and (off == size) == (rc == zsfile.END), (i, len(h), off, size, rc)
-    if rc != zsfile.END:
-        # the image cut where the lister ended lists the same records and ends there
-        ch, crc = ri.host_records(img[:off], A)
-        assert crc == zsfile.END and np.array_equal(ch, h), off
-    return off, take
-
-
-def _host_image(img: bytes):
-    """(records uint64 [n, 4], row words [0..8]) of one image from the host lister."""
-    if len(img) < 40:
-        return np.zeros((0, 4), np.uint64), [EINVAL_WORD, 0, 0, 0, 0, 0, 0, 0, U64_MAX]
-    h, rc = ri.host_records(bytes(img), A)
-    assert rc in (zsfile.END, zsfile.STOPPED, zsfile.TRUNCATED)
-    end, take = _trajectory(bytes(img), h, rc)
-    return h, [rc, len(h), end] + _folds(h) + [take]
-
-
-def _expect(images, descs, took_over=None):
-    """What the one call must give for these images at these places:
-    (recs [n, 4], rows [k, 12], tot[1..7])."""
-    recs, rows, first, bad = [], [], 0, 0
-    for j, (img, (at, size)) in enumerate(zip(images, descs)):
-        assert size == len(img)
-        h, row = _host_image(img)
-        if took_over is not None:        # the builder's own word on where the lister leaves the slots
-            assert row[8] == took_over.get(j, U64_MAX), (j, row[8])
-        r = h.copy()
-        r[:, 0] += np.uint64(at)
-        r[r[:, 2] != U64_MAX, 2] += np.uint64(at)
-        recs.append(r)
-        rows.append(row + [first, 0, 0])
-        first += len(h)
-        bad += row[0] != zsfile.END
-    recs = np.concatenate(recs)
-    return recs, np.array(rows, np.uint64), [first] + _folds(recs) + [bad]
-
-
-def _run(d_arena, descs, cap=None, block=0, tile=0, scratch=None, null_recs=False):
-    """device_records_multi into canary-filled arrays PAD entries longer than
-    needed; the whole arrays come back as numpy uint64."""
-    dev, k = d_arena.device, len(descs)
-    if cap is None:
-        cap = sum(size // 24 + 1 for _, size in descs)
-    room = 0 if null_recs else cap + PAD
-    out = (_canary(32 * room, dev).view(torch.int64).view(room, 4), _canary(8 * (ROW * k + PAD), dev).view(torch.int64),
-           _canary(8 * (TOT + PAD), dev).view(torch.int64))
-    zsfile.device_records_multi(d_arena, descs, cap=cap, block_bytes=block, tile_bytes=tile, out=out, scratch=scratch)
-    recs, rows, tot = (t.cpu().numpy().view(np.uint64) for t in out)
-    return recs.reshape(room, 4), rows, tot, cap
-
-
-def _check(got, exp, what=""):
-    recs, rows, tot, cap = got
-    erecs, erows, etot = exp
-    k, total = len(erows), etot[0]
-    assert np.array_equal(rows[:ROW * k].reshape(k, ROW), erows), (what, rows[:ROW * k].reshape(k, ROW), erows)
-    assert [int(v) for v in tot[:TOT]] == [zsfile.OVERFLOW if total > cap else 0] + etot, (what, tot[:TOT], etot)
-    m = min(total, cap)
-    assert np.array_equal(recs[:m], erecs[:m]), what
-    # nothing at index >= min(total, cap) was written, nor past the rows and the totals
-    assert (recs[m:] == CANARY_WORD).all(), what
-    assert (rows[ROW * k:] == CANARY_WORD).all() and (tot[TOT:] == CANARY_WORD).all(), what
 
 
 def _both(images, gaps=None, took_over=None, dev=None):
@@ -298,13 +219,11 @@ def test_caller_scratch_fenced(gpu, tails):
         d, descs, exp = _both(images, took_over=took, dev=gpu)
         need = zsfile.records_multi_scratch_bytes(descs, block, tile)
         assert need > 0
-        whole = _canary(need + 2 * 4096, gpu)
-        scratch = whole[4096:4096 + need]
+        whole, scratch = dm.fenced(need, gpu)
         assert scratch.data_ptr() % 16 == 0
         mine = _run(d, descs, block=block, tile=tile, scratch=scratch)
         _check(mine, exp, ("caller scratch", block))
-        h = whole.cpu().numpy()
-        assert (h[:4096] == CANARY).all() and (h[4096 + need:] == CANARY).all()
+        assert dm.intact(whole, need)
         lib = _run(d, descs, block=block, tile=tile)
         assert all(np.array_equal(a, b) for a, b in zip(mine[:3], lib[:3]))
 

@@ -8,25 +8,12 @@ import pytest
 
 from oracle import oracle
 from oracle import zs_format as zf
+from tests.images import UUID, UUIDSTR
+from tests.pack_cases import records as _records
 from zeroskip_amd import repack, zsfile
 from zeroskip_amd._lib import ZscrcError, stats
 
 pytestmark = pytest.mark.gpu
-
-UUID = bytes(range(16))
-UUIDSTR = "00010203-0405-0607-0809-0a0b0c0d0e0f"
-
-
-def _records(n, seed, maxval=600, deletes=True):
-    rng = np.random.default_rng(seed)
-    recs = []
-    for i in range(n):
-        key = b"%016d" % (i * 7)
-        if deletes and i % 13 == 4:
-            recs.append((key, None))
-        else:
-            recs.append((key, rng.integers(0, 256, int(rng.integers(0, maxval)), dtype=np.uint8).tobytes()))
-    return recs
 
 
 def _pack(path, recs, chunk=0, start=2, end=9):

@@ -16,41 +16,13 @@ import torch
 
 from oracle import oracle
 from oracle import zs_format as zf
-from tests.test_format_oracle import UUID
+from tests.images import zsbench_db as _zsbench_db
 from zeroskip_amd import zsfile
 from zeroskip_amd._lib import lib
 
 pytestmark = pytest.mark.gpu
 
 RUN_OFF = 2048  # zs::BatchDesc::opt bit: no run rounds
-
-
-def _zsbench_db(per_file, gaps, seed=5):
-    """zsbench BATCHED-like files (one 16-byte key + 256-byte value per
-    transaction: 312-byte spans every 320 bytes) concatenated with `gaps`
-    bytes between them (shifts every file's piece grid)."""
-    rng = np.random.default_rng(seed)
-    parts, offs, lens, commits = [], [], [], []
-    base = 0
-    for f, (n, gap) in enumerate(zip(per_file, gaps)):
-        parts.append(bytes(rng.integers(0, 256, gap, dtype=np.uint8)))
-        base += gap
-        w = zf.FileWriter(UUID, idx=f)
-        for t in range(n):
-            w.add(b"%016d" % (f * 100000 + t), rng.integers(0, 256, 256, dtype=np.uint8).tobytes())
-            w.commit()
-        if f % 2:
-            w.finalise()              # a stale zero-length commit after the last span
-        img = w.image()
-        cs, _, _ = zf.walk(img)
-        for c in cs:
-            offs.append(base + c["span_off"])
-            lens.append(c["span_len"])
-            commits.append(c)
-        parts.append(img)
-        base += len(img)
-    host = np.frombuffer(b"".join(parts), np.uint8).copy()
-    return host, np.array(offs, np.int64), np.array(lens, np.int64), commits
 
 
 def _verify(d, o, ln, opt, **kw):

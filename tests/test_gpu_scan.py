@@ -11,78 +11,39 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import find_cases as fc
 from tests import scan_cases as sc
+from tests.images import REF, U64_MAX, UUIDSTR
 from zeroskip_amd import repack, zsfile
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "tests", "golden", "ref_format")
-UUIDSTR = "00010203-0405-0607-0809-0a0b0c0d0e0f"
-U64_MAX = sc.U64_MAX
 U64 = np.uint64
-CANARY = 0xA5
-PAD = 4096
 SPLITS = [1, 2, 64, 2048, 0]      # no table, the smallest, a middle one, the largest, the default
-
-
-def _dev_bytes(b: bytes, dev, shift: int = 0) -> torch.Tensor:
-    """The bytes in device memory at an address = shift mod 16 (an empty tensor for none)."""
-    buf = torch.zeros(len(b) + 32, dtype=torch.uint8, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    d = buf[shift:shift + len(b)]
-    if len(b):
-        d.copy_(torch.from_numpy(np.frombuffer(b, dtype=np.uint8).copy()))
-    return d
-
-
-def _dev_recs(recs: np.ndarray, dev) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(recs).view(np.int64).reshape(-1, 4).copy()).to(dev)
-
-
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
-
-
-def _inside(whole, nbytes):
-    """The bytes between the fences, which must hold."""
-    h = whole.cpu().numpy()
-    assert bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all())
-    return h[PAD:PAD + nbytes]
-
-
-def _dev_in(case, dev, shift=0, qshift=0):
-    return (_dev_bytes(case.src, dev, shift), [(_dev_recs(r, dev), b) for r, b in case.levels],
-            _dev_bytes(case.qsrc, dev, qshift), _dev_recs(case.queries, dev))
 
 
 def _scan(case, dev, cap, cand_cap, splitters=0, keep=False, check_order=False, scratch=None, dev_in=None):
     """device_scan into canary buffers between fences: (rows bytes [32 cap],
     offs bytes [8 (nq + 1)], seqs bytes [8 cap], res uint64 [12])."""
-    d_src, levels, d_qsrc, queries = dev_in or _dev_in(case, dev)
+    d_src, levels, d_qsrc, queries = dev_in or dm.dev_in(case, dev)
     nq = int(queries.shape[0])
-    wr, rows = _fenced(32 * cap, dev)
-    wo, offs = _fenced(8 * (nq + 1), dev)
-    ws, seqs = _fenced(8 * cap, dev)
+    wr, rows = dm.fenced(32 * cap, dev)
+    wo, offs = dm.fenced(8 * (nq + 1), dev)
+    ws, seqs = dm.fenced(8 * cap, dev)
     res = torch.full((zsfile.SCAN_RES_WORDS,), -6, dtype=torch.int64, device=dev)
     zsfile.device_scan(d_src, levels, d_qsrc, queries, keep_deletes=keep, check_order=check_order, cap=cap,
                        cand_cap=cand_cap, splitters=splitters,
                        out=(rows.view(torch.int64).view(cap, 4), offs.view(torch.int64), seqs.view(torch.int64), res),
                        scratch=scratch)
-    return (_inside(wr, 32 * cap), _inside(wo, 8 * (nq + 1)), _inside(ws, 8 * cap),
+    return (dm.inside(wr, 32 * cap), dm.inside(wo, 8 * (nq + 1)), dm.inside(ws, 8 * cap),
             [int(v) for v in res.cpu().numpy().view(U64)])
-
-
-def _all_canary(*arrays):
-    return all(bool((a == CANARY).all()) for a in arrays)
 
 
 def _same(case, dev, keeps=(False, True), splits=SPLITS, check_order=False, shift=0, qshift=0, host=True):
     """The case at every table size: equal byte for byte to the model, and the
     model to the host scan; two rows of room past the last stay untouched."""
-    dev_in = _dev_in(case, dev, shift, qshift)
+    dev_in = dm.dev_in(case, dev, shift, qshift)
     for keep in keeps:
         wrows, woffs, wseqs, wres = case.model(keep)
         if host:
@@ -96,7 +57,7 @@ def _same(case, dev, keeps=(False, True), splits=SPLITS, check_order=False, shif
             assert res == wres, (what, res, wres)
             assert offs.tobytes() == woffs.tobytes(), what
             assert rows[:32 * m].tobytes() == wrows.tobytes() and seqs[:8 * m].tobytes() == wseqs.tobytes(), what
-            assert _all_canary(rows[32 * m:], seqs[8 * m:]), what
+            assert dm.all_canary(rows[32 * m:], seqs[8 * m:]), what
         if keep:
             assert wres[2] + wres[4] == wres[3]
         else:
@@ -151,7 +112,7 @@ def test_candidate_counts_around_the_grid(gpu):
         _same(c, gpu, keeps=(True,), host=False)
         # deletes dropped: against the host scan (which test_scan_host.py holds against the model)
         got = zsfile.scan(c.src, c.levels, c.qsrc, c.queries)
-        dev_in = _dev_in(c, gpu)
+        dev_in = dm.dev_in(c, gpu)
         for s in SPLITS:
             rows, offs, seqs, res = _scan(c, gpu, int(got[3][2]), int(got[3][3]), s, False, dev_in=dev_in)
             assert rows.tobytes() == got[0].tobytes() and offs.tobytes() == got[1].tobytes() and \
@@ -198,43 +159,43 @@ def test_random_cases(gpu):
 # ------------------------------------------------------------- refusals, overflows
 def test_a_record_outside_the_source(gpu):
     case, seq = sc.bad_record_case()
-    dev_in = _dev_in(case, gpu)
+    dev_in = dm.dev_in(case, gpu)
     for s in SPLITS:
         for check_order in (False, True):
             rows, offs, seqs, res = _scan(case, gpu, 8, 64, s, check_order=check_order, dev_in=dev_in)
             assert res == [sc.EINVAL64, seq] + [0] * 10
-            assert _all_canary(rows, offs, seqs)
+            assert dm.all_canary(rows, offs, seqs)
 
 
 def test_check_order(gpu):
     case = sc.unordered_case()
-    dev_in = _dev_in(case, gpu)
+    dev_in = dm.dev_in(case, gpu)
     for s in SPLITS:
         rows, offs, seqs, res = _scan(case, gpu, 64, 128, s, check_order=True, dev_in=dev_in)
         assert res == [sc.EINVAL64, 2] + [0] * 5 + [1] + [0] * 4
-        assert _all_canary(rows, offs, seqs)
+        assert dm.all_canary(rows, offs, seqs)
     # a bounds offence goes before an order offence at a smaller seq
     recs = case.levels[0][0].copy()
     recs[6, 1] = len(case.src)
     both = sc.ScanCase("both", case.src, [(recs, 0), case.levels[1]], case.qsrc, case.queries)
     for s in SPLITS:
         rows, offs, seqs, res = _scan(both, gpu, 64, 128, s, check_order=True)
-        assert res == [sc.EINVAL64, 6] + [0] * 10 and _all_canary(rows, offs, seqs)
+        assert res == [sc.EINVAL64, 6] + [0] * 10 and dm.all_canary(rows, offs, seqs)
 
 
 def test_a_level_that_does_not_ascend_stays_inside_its_buffers(gpu):
     """Without CHECK_ORDER: the rows are unspecified; the fences of the outputs
     and of the scratch hold and the code is 0."""
     for case in (sc.unordered_case(), sc.shuffled_case(0)):
-        dev_in = _dev_in(case, gpu)
+        dev_in = dm.dev_in(case, gpu)
         cands = case.n * len(case.queries)         # the most there can be, whatever a bisection makes of the level
         for s in SPLITS:
             for keep in (False, True):
                 need = zsfile.device_scan_scratch_bytes(len(case.queries), len(case.levels), cands, s)
-                whole, scratch = _fenced(need, gpu)
+                whole, scratch = dm.fenced(need, gpu)
                 rows, offs, seqs, res = _scan(case, gpu, cands, cands, s, keep, scratch=scratch, dev_in=dev_in)
                 assert res[0] == 0 and res[1] == len(case.queries) and res[2] <= res[3] <= cands
-                _inside(whole, need)
+                dm.inside(whole, need)
 
 
 def test_candidate_overflow(gpu, cases):
@@ -243,11 +204,11 @@ def test_candidate_overflow(gpu, cases):
     wrows, woffs, wseqs, wres = c.model(False)
     cands, m = wres[3], len(wrows)
     assert cands > 1000
-    dev_in = _dev_in(c, gpu)
+    dev_in = dm.dev_in(c, gpu)
     for s in SPLITS:
         rows, offs, seqs, res = _scan(c, gpu, m, cands - 1, s, dev_in=dev_in)
         assert res == [sc.OVERFLOW, len(c.queries), 0, cands, 0, 0, 0, 1, 0, 0, 0, 0]
-        assert _all_canary(rows, offs, seqs)
+        assert dm.all_canary(rows, offs, seqs)
         rows, offs, seqs, res = _scan(c, gpu, m, cands, s, dev_in=dev_in)
         assert res == wres and rows.tobytes() == wrows.tobytes() and offs.tobytes() == woffs.tobytes()
     # the wrapper sizes itself: from the levels' records, then from the reported count
@@ -262,7 +223,7 @@ def test_row_overflow(gpu, cases):
     """cap = rows - 1 and cap = 0: d_offs in full, exactly the rows below cap."""
     for name in ("prefixes", "winners", "n65", "c1025"):
         c = cases[name]
-        dev_in = _dev_in(c, gpu)
+        dev_in = dm.dev_in(c, gpu)
         for keep in (False, True):
             wrows, woffs, wseqs, wres = c.model(keep)
             m = len(wrows)
@@ -289,18 +250,18 @@ def test_caller_scratch_fenced(gpu, cases):
         wrows, woffs, wseqs, wres = c.model(False)
         need = zsfile.device_scan_scratch_bytes(len(c.queries), len(c.levels), wres[3], s)
         assert need > 0
-        whole, scratch = _fenced(need, gpu)
+        whole, scratch = dm.fenced(need, gpu)
         assert scratch.data_ptr() % 16 == 0
         rows, offs, seqs, res = _scan(c, gpu, len(wrows), wres[3], s, scratch=scratch)
         assert res == wres and rows.tobytes() == wrows.tobytes() and offs.tobytes() == woffs.tobytes() and \
             seqs.tobytes() == wseqs.tobytes(), name
-        _inside(whole, need)
+        dm.inside(whole, need)
 
 
 def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     """A walk and a scan on two streams share the library's scratch, ordered by its event."""
     from tests import records_images as ri
-    d_img = _dev_bytes(ri.wellformed(), gpu)
+    d_img = dm.dev_bytes(ri.wellformed(), gpu)
 
     def listed(walked):
         off, ln, res = (t.cpu().numpy() for t in walked)
@@ -309,7 +270,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
     want_walk = listed(zsfile.device_walk(d_img))
     assert want_walk[2][1] > 0
     c = cases["n65"]
-    dev_in = _dev_in(c, gpu)
+    dev_in = dm.dev_in(c, gpu)
     wrows, woffs, wseqs, wres = c.model(False)
     s1, s2 = torch.cuda.Stream(device=gpu), torch.cuda.Stream(device=gpu)
     torch.cuda.synchronize(gpu)
@@ -327,7 +288,7 @@ def test_library_scratch_behind_a_walk_on_another_stream(gpu, cases):
 
 def test_two_runs_bit_for_bit(gpu, cases):
     for c, s in ((cases["n65"], 64), (cases["many_levels"], 0), (sc.random_case(1), 2)):
-        dev_in = _dev_in(c, gpu)
+        dev_in = dm.dev_in(c, gpu)
         wres = c.model(True)[3]
         a = _scan(c, gpu, wres[2], wres[3], s, True, dev_in=dev_in)
         b = _scan(c, gpu, wres[2], wres[3], s, True, dev_in=dev_in)
@@ -342,7 +303,7 @@ def _values(case, rows):
 def test_rows_into_the_gather(gpu):
     """device_scan's rows are device_gather's items as they stand: the values equal the model's."""
     c = sc.random_case(2)
-    dev_in = _dev_in(c, gpu)
+    dev_in = dm.dev_in(c, gpu)
     for keep in (False, True):
         wrows = c.model(keep)[0]
         rows, offs, seqs, res = zsfile.device_scan(*dev_in, keep_deletes=keep)
@@ -356,9 +317,9 @@ def test_rows_into_the_gather(gpu):
 def test_rows_as_a_level_of_the_lookup(gpu):
     """The rows of an empty-prefix scan are a level: every row key is found at its own index."""
     c = sc.random_case(3)
-    d_src, levels, _, _ = _dev_in(c, gpu)
+    d_src, levels, _, _ = dm.dev_in(c, gpu)
     qsrc, queries = fc.lay_queries([b""])
-    rows, offs, seqs, res = zsfile.device_scan(d_src, levels, _dev_bytes(qsrc, gpu), _dev_recs(queries, gpu),
+    rows, offs, seqs, res = zsfile.device_scan(d_src, levels, dm.dev_bytes(qsrc, gpu), dm.dev_recs(queries, gpu),
                                                keep_deletes=True, check_order=True)
     n = int(res[2])
     assert n == len(rows) > 500
@@ -370,9 +331,9 @@ def test_rows_as_a_level_of_the_lookup(gpu):
 def test_the_empty_prefix_scan_is_the_merge_reversed(gpu):
     """The merge lets the later list win, the scan the earlier level: byte for byte equal, deletes dropped or kept."""
     for c in (sc.random_case(0), sc.random_case(3), sc.winners_case(), sc.twice_case()):
-        d_src, levels, _, _ = _dev_in(c, gpu)
+        d_src, levels, _, _ = dm.dev_in(c, gpu)
         qsrc, queries = fc.lay_queries([b""])
-        d_qsrc, d_q = _dev_bytes(qsrc, gpu), _dev_recs(queries, gpu)
+        d_qsrc, d_q = dm.dev_bytes(qsrc, gpu), dm.dev_recs(queries, gpu)
         for keep in (False, True):
             rows, offs, seqs, res = zsfile.device_scan(d_src, levels, d_qsrc, d_q, keep_deletes=keep)
             merged, mres = repack.device_merge(d_src, levels[::-1], drop_deletes=not keep)
@@ -383,7 +344,7 @@ def test_the_empty_prefix_scan_is_the_merge_reversed(gpu):
 
 def test_foreach_end_to_end(gpu):
     c = sc.winners_case()
-    dev_in = _dev_in(c, gpu)
+    dev_in = dm.dev_in(c, gpu)
     wrows, woffs, _, wres = c.model(False)
     rows, offs, values, voffs, crcs, sres, gres = zsfile.device_foreach(*dev_in, crcs=True)
     assert [int(v) for v in sres.cpu().numpy().view(U64)] == wres and int(gres[0]) == 0
@@ -397,7 +358,7 @@ def test_foreach_end_to_end(gpu):
                                                            for x in got]
     # a refused scan runs no gather
     bad, _ = sc.bad_record_case()
-    out = zsfile.device_foreach(*_dev_in(bad, gpu))
+    out = zsfile.device_foreach(*dm.dev_in(bad, gpu))
     assert int(out[5][0]) == -1 and out[2] is None and out[6] is None
 
 
@@ -417,13 +378,13 @@ def test_reference_repack_inputs(gpu, tmp_path, name):
     assert rep["branch"] == 2 and rep["files_merged"] == 2
     want = zf.packed_records(open(rep["path"], "rb").read())
     arena = older + bytes(-len(older) % 64) + newer
-    d_arena = _dev_bytes(arena, gpu)
+    d_arena = dm.dev_bytes(arena, gpu)
     levels = []
     for off, img in ((0, older), (len(arena) - len(newer), newer)):
         recs, res = zsfile.device_records(d_arena[off:off + len(img)], zsfile.PACKED)
         levels.append((recs[:int(res[1])].contiguous(), off))
     qsrc, queries = fc.lay_queries([b""])
-    rows, offs, seqs, res = zsfile.device_scan(d_arena, levels, _dev_bytes(qsrc, gpu), _dev_recs(queries, gpu),
+    rows, offs, seqs, res = zsfile.device_scan(d_arena, levels, dm.dev_bytes(qsrc, gpu), dm.dev_recs(queries, gpu),
                                                check_order=True)
     got = [(arena[ko:ko + kl], arena[vo:vo + vl]) for ko, kl, vo, vl in rows.cpu().tolist()]
     assert got == want and len(got) == rep["records_out"] > 400
@@ -444,9 +405,9 @@ def test_more_prefixes_than_the_bounds_grid_has_threads(gpu):
     wres = [int(v) for v in want[3]]
     assert wres[0] == 0 and wres[1] == nq and wres[4] > 0 and wres[5] > 0 and wres[2] > nq // 2
     assert int(want[1][-1]) > int(want[1][zsfile.FIND_GRID_THREADS]) > 0          # rows past the first trip
-    d_src = _dev_bytes(src, gpu)
-    d_levels = [(_dev_recs(r, gpu), b) for r, b in levels]
-    d_q = _dev_recs(queries, gpu)
+    d_src = dm.dev_bytes(src, gpu)
+    d_levels = [(dm.dev_recs(r, gpu), b) for r, b in levels]
+    d_q = dm.dev_recs(queries, gpu)
     for s in (0, 1, 2048):
         rows, offs, seqs, res = zsfile.device_scan(d_src, d_levels, d_src, d_q, cap=wres[2], cand_cap=wres[3],
                                                    splitters=s)
@@ -479,9 +440,9 @@ def test_a_million_candidates(gpu):
     want = zsfile.scan(src, levels, qsrc, queries)
     wres = [int(v) for v in want[3]]
     assert wres[0] == 0 and wres[3] > zsfile.SCAN_GRID_THREADS * 2 and wres[4] > 0 and wres[5] > 0
-    d_src, d_qsrc = _dev_bytes(src.tobytes(), gpu), _dev_bytes(qsrc.tobytes(), gpu)
-    d_levels = [(_dev_recs(r, gpu), b) for r, b in levels]
-    rows, offs, seqs, res = zsfile.device_scan(d_src, d_levels, d_qsrc, _dev_recs(queries, gpu), cap=wres[2],
+    d_src, d_qsrc = dm.dev_bytes(src.tobytes(), gpu), dm.dev_bytes(qsrc.tobytes(), gpu)
+    d_levels = [(dm.dev_recs(r, gpu), b) for r, b in levels]
+    rows, offs, seqs, res = zsfile.device_scan(d_src, d_levels, d_qsrc, dm.dev_recs(queries, gpu), cap=wres[2],
                                                cand_cap=wres[3])
     assert res.cpu().numpy().tolist() == want[3].tolist()
     assert rows.cpu().numpy().tobytes() == want[0].tobytes() and offs.cpu().numpy().tobytes() == want[1].tobytes()

@@ -21,13 +21,18 @@ from tests import gather_cases as gc
 from tests import huge_cases as hc
 from tests import records_images as ri
 from tests import walk_images as wi
-from tests.test_gpu_records import _folds
-from tests.test_gpu_records_multi import _check as _records_check
-from tests.test_gpu_records_multi import _run as _records_run
-from tests.test_gpu_records_multi import _trajectory
-from tests.test_gpu_walk_multi import _check as _walk_check
-from tests.test_gpu_walk_multi import _first_unaligned
-from tests.test_gpu_walk_multi import _run as _walk_run
+from tests.arena_cases import first_unaligned as _first_unaligned
+from tests.arena_cases import records_check as _records_check
+from tests.arena_cases import records_run as _records_run
+from tests.arena_cases import trajectory as _trajectory
+from tests.arena_cases import walk_check as _walk_check
+from tests.arena_cases import walk_run as _walk_run
+from tests.devmem import CANARY, PAD
+from tests.devmem import dev_recs as _dev_recs
+from tests.devmem import fenced as _fenced
+from tests.devmem import inside as _inside
+from tests.images import UUID
+from tests.records_images import folds as _folds
 from zeroskip_amd import repack, zsfile
 from zeroskip_amd._lib import lib
 
@@ -35,34 +40,15 @@ pytestmark = pytest.mark.gpu
 
 U64 = np.uint64
 B31, B32 = hc.B31, hc.B32
-CANARY = 0xA5
-PAD = 4096
 MIB = 1 << 20
 A, F, P = zsfile.ACTIVE, zsfile.FINALISED, zsfile.PACKED
-UUID = bytes(range(16))
 HUGE_VALUE = (37, B32 + 5 * MIB + 3)         # (val_off, val_len) of the gather's and the packer's huge record
 MEDIUM = MIB + 1
 LIST_CAP = 8192                              # more records than any image here holds
 
 
-def _dev_recs(recs: np.ndarray, dev) -> torch.Tensor:
-    return torch.from_numpy(np.ascontiguousarray(recs).view(np.int64).reshape(-1, 4).copy()).to(dev)
-
-
 def _dev_lists(lists, dev) -> list:
     return [(_dev_recs(r, dev), b) for r, b in lists]
-
-
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
-
-
-def _inside(whole: torch.Tensor, nbytes: int, what=None) -> np.ndarray:
-    """A small fenced buffer's inside on the host, its fences checked."""
-    h = whole.cpu().numpy()
-    assert bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all()), what
-    return h[PAD:PAD + nbytes]
 
 
 def _canary_on_device(t: torch.Tensor) -> bool:

@@ -45,8 +45,8 @@ import torch
 from oracle import oracle
 from oracle import zs_format as zf
 from tests import walk_images as wi
-from tests.test_format_oracle import UUID
-from tests.test_gpu_nbv import _oracle_bad
+from tests.images import UUID
+from tests.images import oracle_bad as _oracle_bad
 from zeroskip_amd import zsfile
 from zeroskip_amd._lib import LEN_UNBOUNDED, check, lib, stats
 
@@ -428,7 +428,7 @@ def test_cpass_create_beside_a_side_stream(gpu):
     stale short ones.  The caller's max_len -- the host walk's, the true
     maximum -- must then be the bound the verdict runs with: the corrupted
     longest commit is listed."""
-    from tests.test_consistent_host import small_db
+    from tests.consistent_cases import small_db
     from zeroskip_amd import consistent as cs
     from zeroskip_amd import device as zd
     job = cs.Consistent(cs.open_db(small_db(long_region=True)), 0, 1).prepare()
@@ -470,7 +470,7 @@ def test_cpass_passes_on_special_handles(gpu):
     hipStreamLegacy, NULL and the per-thread handle twice in a row: every
     result is the first, synchronous one's, which lists the corrupted commit
     -- counted once per pass."""
-    from tests.test_consistent_host import small_db
+    from tests.consistent_cases import small_db
     from zeroskip_amd import consistent as cs
     job = cs.Consistent(cs.open_db(small_db(long_region=True)), 0, 1).prepare()
     i = int(torch.argmax(job.d_len))

@@ -12,10 +12,17 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import fuzzlib
-from tests.test_format_oracle import UUID, build_active
+from tests.devmem import CANARY
+from tests.images import U64_MAX, UUID, build_active
 from tests.walk_images import (NEW_GEOMETRIES, NEW_GEOMETRY_IDS, Img, boundary_cases, long_commit,  # noqa: F401
                                long_key, short_commit, unaligned_image, unaligned_tail_image)
+from tests.walk_images import dev_image as _dev
+from tests.walk_images import device_walk as _device
+from tests.walk_images import host_walk as _host
+from tests.walk_images import same_walk as _same
+from tests.walk_images import u64 as _u64
 from zeroskip_amd import zsfile
 
 pytestmark = pytest.mark.gpu
@@ -27,41 +34,6 @@ SMALL = OPTSETS[1:]
 # with every other number of slots per tile, block == tile and one block for the whole image
 GEOMETRIES = OPTSETS + NEW_GEOMETRIES
 GEOMETRY_IDS = OPT_IDS + NEW_GEOMETRY_IDS
-U64_MAX = (1 << 64) - 1
-PAD = 4096
-CANARY = 0xA5
-
-
-def _dev(img: bytes, dev) -> torch.Tensor:
-    return torch.from_numpy(np.frombuffer(img, dtype=np.uint8).copy()).to(dev)
-
-
-def _host(img: bytes):
-    off, ln, rc, end = zsfile.walk(img)
-    return off.astype(np.uint64), ln.astype(np.uint64), rc, end
-
-
-def _u64(t: torch.Tensor) -> np.ndarray:
-    return t.cpu().numpy().view(np.uint64)
-
-
-def _device(d, block=0, tile=0, serial=False):
-    off, ln, res = zsfile.device_walk(d, block_bytes=block, tile_bytes=tile, serial=serial)
-    r = _u64(res)
-    n = int(r[1])
-    return _u64(off[:n]), _u64(ln[:n]), r
-
-
-def _same(img: bytes, d, block, tile, serial=False):
-    """The device walk of d equals the host walk of img; returns its res."""
-    hoff, hlen, hrc, hend = _host(img)
-    off, ln, r = _device(d, block, tile, serial)
-    what = (len(img), block, tile, serial)
-    assert (int(r[0]), int(r[1]), int(r[2])) == (hrc, len(hoff), hend), what
-    assert np.array_equal(off, hoff) and np.array_equal(ln, hlen), what
-    assert int(r[3]) == (int(hlen.max()) if len(hlen) else 0), what
-    assert int(r[4]) == (int(hlen.min()) if len(hlen) else 0), what
-    return r
 
 
 @pytest.fixture(scope="module")
@@ -148,16 +120,6 @@ def test_unaligned_continuation(gpu, wellformed, block, tile):
     assert int(r[5]) == U64_MAX  # the whole walk was the one-lane one
 
 
-def _fenced(nbytes: int, dev):
-    whole = torch.full((nbytes + 2 * PAD,), CANARY, dtype=torch.uint8, device=dev)
-    return whole, whole[PAD:PAD + nbytes]
-
-
-def _intact(whole: torch.Tensor, nbytes: int) -> bool:
-    h = whole.cpu().numpy()
-    return bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all())
-
-
 @pytest.mark.parametrize("block,tile", GEOMETRIES, ids=GEOMETRY_IDS)
 def test_cap(gpu, wellformed, block, tile):
     img = wellformed
@@ -167,9 +129,9 @@ def test_cap(gpu, wellformed, block, tile):
     for cap in (n // 2, 0):
         # cap 0 too gets real arrays (one entry's room): nothing may be stored there
         room = max(cap, 1) * 8
-        fo, off = _fenced(room, gpu)
-        fl, ln = _fenced(room, gpu)
-        fr, res = _fenced(8 * zsfile.WALK_RES_WORDS, gpu)
+        fo, off = dm.fenced(room, gpu)
+        fl, ln = dm.fenced(room, gpu)
+        fr, res = dm.fenced(8 * zsfile.WALK_RES_WORDS, gpu)
         assert off.data_ptr() and ln.data_ptr()
         zsfile.device_walk(d, cap=cap, block_bytes=block, tile_bytes=tile,
                            out=(off.view(torch.int64), ln.view(torch.int64), res.view(torch.int64)))
@@ -180,7 +142,7 @@ def test_cap(gpu, wellformed, block, tile):
         assert np.array_equal(_u64(ln.view(torch.int64))[:cap], hlen[:cap])
         if cap == 0:  # the entry the arrays have room for is untouched
             assert bool((off == CANARY).all()) and bool((ln == CANARY).all())
-        assert _intact(fo, room) and _intact(fl, room) and _intact(fr, 8 * zsfile.WALK_RES_WORDS)
+        assert dm.intact(fo, room) and dm.intact(fl, room) and dm.intact(fr, 8 * zsfile.WALK_RES_WORDS)
     # cap 0 with no arrays at all (the pointers may be NULL then)
     _, _, res = zsfile.device_walk(d, cap=0, block_bytes=block, tile_bytes=tile,
                                    out=(torch.empty(0, dtype=torch.int64, device=gpu),
@@ -204,9 +166,9 @@ def test_unaligned_tail(gpu, wellformed, block, tile):
     r = _same(img, d, block, tile)
     assert int(r[5]) == first
     for cap in (n0 - 1, n0, n0 + 1, n0 + 3, n0 + 4, n0 + 5):
-        fo, off = _fenced(cap * 8, gpu)
-        fl, ln = _fenced(cap * 8, gpu)
-        fr, res = _fenced(8 * zsfile.WALK_RES_WORDS, gpu)
+        fo, off = dm.fenced(cap * 8, gpu)
+        fl, ln = dm.fenced(cap * 8, gpu)
+        fr, res = dm.fenced(8 * zsfile.WALK_RES_WORDS, gpu)
         zsfile.device_walk(d, cap=cap, block_bytes=block, tile_bytes=tile,
                            out=(off.view(torch.int64), ln.view(torch.int64), res.view(torch.int64)))
         r = _u64(res.view(torch.int64))
@@ -219,7 +181,7 @@ def test_unaligned_tail(gpu, wellformed, block, tile):
         assert np.array_equal(_u64(ln.view(torch.int64))[:m], hlen[:m]), what
         # room past the last span (cap n + 1) stays untouched
         assert bool((off[8 * m:] == CANARY).all()) and bool((ln[8 * m:] == CANARY).all()), what
-        assert _intact(fo, cap * 8) and _intact(fl, cap * 8) and _intact(fr, 8 * zsfile.WALK_RES_WORDS), what
+        assert dm.intact(fo, cap * 8) and dm.intact(fl, cap * 8) and dm.intact(fr, 8 * zsfile.WALK_RES_WORDS), what
 
 
 def test_serial_flag_on_wellformed(gpu, wellformed):
@@ -232,13 +194,13 @@ def test_caller_scratch_fenced(gpu, wellformed, block, tile):
     hoff, hlen, hrc, hend = _host(img)
     need = zsfile.walk_scratch_bytes(len(img), block, tile)
     assert need > 0
-    whole, scratch = _fenced(need, gpu)
+    whole, scratch = dm.fenced(need, gpu)
     assert scratch.data_ptr() % 16 == 0
     off, ln, res = zsfile.device_walk(_dev(img, gpu), block_bytes=block, tile_bytes=tile, scratch=scratch)
     r = _u64(res)
     assert (int(r[0]), int(r[1]), int(r[2])) == (hrc, len(hoff), hend)
     assert np.array_equal(_u64(off[:len(hoff)]), hoff) and np.array_equal(_u64(ln[:len(hoff)]), hlen)
-    assert _intact(whole, need)
+    assert dm.intact(whole, need)
 
 
 def test_scratch_bytes_bound(gpu):

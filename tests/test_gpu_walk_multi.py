@@ -14,189 +14,28 @@ import torch
 
 from oracle import zs_format as zf
 from tests import fuzzlib
+from tests import devmem as dm
 from tests import walk_images as wi
-from tests.test_format_oracle import UUID, build_active
+from tests.arena_cases import arena as _arena
+from tests.arena_cases import finalised as _finalised
+from tests.arena_cases import key70k as _key70k
+from tests.arena_cases import stopped as _stopped
+from tests.arena_cases import walk_check as _check
+from tests.arena_cases import walk_expect as _expect
+from tests.arena_cases import walk_run as _run
+from tests.images import U64_MAX, UUID, build_active
 from zeroskip_amd import zsfile
 
 pytestmark = pytest.mark.gpu
 
 GEOMETRIES = [(0, 0), (64, 64), (512, 64), (4096, 512), (8192, 1024), (16384, 16384)]
 GEOMETRY_IDS = ["default", "b64_t64", "b512_t64", "b4096_t512", "b8192_t1024", "b16384_t16384"]
-U64_MAX = (1 << 64) - 1
-EINVAL_WORD = (1 << 64) - 1          # (uint64_t)(int64_t)ZSCRC_EINVAL
-PAD = 64                             # entries behind every output array
-CANARY = 0xA5
-CANARY_WORD = int.from_bytes(bytes([CANARY]) * 8, "little")
 
 
 # ------------------------------------------------------------------ helpers
-def _arena(images, gaps=None):
-    """The images in one uint8 buffer with canary bytes before, between and
-    after them: (buffer, [(off, size)]).  gaps[i] = the canary bytes before
-    image i; by default the least number from 8 up that puts image i at an
-    offset == i (mod 8), so the offsets take every residue in turn."""
-    parts, descs, pos = [], [], 0
-    for i, img in enumerate(images):
-        gap = gaps[i] if gaps is not None else 8 + (i - pos - 8) % 8
-        parts.append(bytes([CANARY]) * gap)
-        pos += gap
-        assert gaps is not None or pos % 8 == i % 8
-        descs.append((pos, len(img)))
-        parts.append(bytes(img))
-        pos += len(img)
-    parts.append(bytes([CANARY]) * 72)
-    return np.frombuffer(b"".join(parts), dtype=np.uint8).copy(), descs
-
-
-def _first_unaligned(img: bytes, rc: int, end: int, n: int) -> int:
-    """Row word [5] from the bytes alone: zscrc_zs_walk's loop restated to
-    list the offsets it passes (checked here to end as the host walk did);
-    the first one that is no multiple of 8 is where a one-lane walk has to
-    take over, U64_MAX if there is none."""
-    size, off, commits = len(img), 40, 0
-
-    def be64(o):
-        return int.from_bytes(img[o:o + 8], "big")
-
-    def rup8(v):
-        return (v + 7) & ~7
-
-    def done(code, unaligned=U64_MAX):
-        assert (code, off, commits) == (rc, end, n), (code, off, commits, rc, end, n)
-        return unaligned
-
-    while off < size:
-        if off % 8:
-            assert off <= end and commits <= n
-            return off                   # the host walk vouches for the rest
-        room = size - off
-        if room < 8:
-            return done(zsfile.TRUNCATED)
-        w = be64(off)
-        t = w >> 56
-        if t in (zf.REC_KEY, zf.REC_LONG_KEY):
-            if t == zf.REC_LONG_KEY and room < 24:
-                return done(zsfile.TRUNCATED)
-            voff = w & 0xFFFFFFFF if t == zf.REC_KEY else be64(off + 16)
-            if voff == 0 or voff > room or room - voff < 16:
-                return done(zsfile.TRUNCATED)
-            v = off + voff
-            vw = be64(v)
-            vlen = (vw >> 32) & 0xFFFFFF if vw >> 56 == zf.REC_VALUE else be64(v + 8)
-            if vlen > size - v - 16 or rup8(vlen) > size - v - 16:
-                return done(zsfile.TRUNCATED)
-            off = v + 16 + rup8(vlen)
-        elif t in (64, 32):              # a delete record, short and long
-            if room < 24:
-                return done(zsfile.TRUNCATED)
-            klen = (w >> 40) & 0xFFFF if t == 64 else be64(off + 8)
-            if klen > room - 24 or rup8(klen) > room - 24:
-                return done(zsfile.TRUNCATED)
-            off += 24 + rup8(klen)
-        elif t == zf.REC_COMMIT:
-            if (w >> 32) & 0xFFFFFF > off:
-                return done(zsfile.TRUNCATED)
-            commits += 1
-            off += 8
-        elif t == zf.REC_LONG_COMMIT:
-            if room < 24 or be64(off + 8) > off:
-                return done(zsfile.TRUNCATED)
-            commits += 1
-            off += 24
-        else:
-            return done(zsfile.STOPPED)
-    return done(zsfile.END, off if off % 8 else U64_MAX)
-
-
-def _host_row(img: bytes):
-    """(off, len, row words [0..5]) of one image from the host walk."""
-    if len(img) < 40:
-        z = np.empty(0, np.uint64)
-        return z, z, [EINVAL_WORD, 0, 0, 0, 0, U64_MAX]
-    off, ln, rc, end = wi.host_walk(img)
-    assert rc in (zsfile.END, zsfile.STOPPED, zsfile.TRUNCATED)
-    return off, ln, [rc, len(off), end, int(ln.max()) if len(ln) else 0, int(ln.min()) if len(ln) else 0,
-                     _first_unaligned(bytes(img), rc, end, len(off))]
-
-
-def _expect(images, descs, took_over=None):
-    """What the multi-walk must give for these images at these places, from
-    the host walk of each: (off, len, img, rows, tot[1..3])."""
-    offs, lens, imgs, rows, first = [], [], [], [], 0
-    for j, (img, (at, size)) in enumerate(zip(images, descs)):
-        assert size == len(img)
-        off, ln, row = _host_row(img)
-        if took_over is not None:        # the builder's own word on where the walk leaves the slots
-            assert row[5] == took_over.get(j, U64_MAX), (j, row[5])
-        offs.append(off + np.uint64(at))
-        lens.append(ln)
-        imgs.append(np.full(len(off), j, np.uint32))
-        rows.append(row + [first, 0])
-        first += len(off)
-    ln = np.concatenate(lens)
-    tot = [first, int(ln.max()) if first else 0, int(ln.min()) if first else 0]
-    return np.concatenate(offs), ln, np.concatenate(imgs), np.array(rows, np.uint64), tot
-
-
-def _canary(n_bytes: int, dev) -> torch.Tensor:
-    return torch.full((n_bytes,), CANARY, dtype=torch.uint8, device=dev)
-
-
-def _run(d_arena, descs, cap=None, block=0, tile=0, scratch=None, null_arrays=False):
-    """device_walk_multi into canary-filled arrays PAD entries longer than
-    needed; the whole arrays come back as numpy (uint64 / uint32)."""
-    dev, k = d_arena.device, len(descs)
-    if cap is None:
-        cap = sum(size // 8 + 1 for _, size in descs)
-    room = 0 if null_arrays else cap + PAD
-    out = (_canary(8 * room, dev).view(torch.int64), _canary(8 * room, dev).view(torch.int64),
-           _canary(4 * room, dev).view(torch.int32), _canary(8 * (8 * k + PAD), dev).view(torch.int64),
-           _canary(8 * (zsfile.WALK_TOT_WORDS + PAD), dev).view(torch.int64))
-    zsfile.device_walk_multi(d_arena, descs, cap=cap, block_bytes=block, tile_bytes=tile, out=out, scratch=scratch)
-    off, ln, img, rows, tot = (t.cpu().numpy() for t in out)
-    return off.view(np.uint64), ln.view(np.uint64), img.view(np.uint32), rows.view(np.uint64), tot.view(np.uint64), cap
-
-
-def _check(got, exp, what=""):
-    off, ln, img, rows, tot, cap = got
-    eoff, eln, eimg, erows, (total, mx, mn) = exp
-    k = len(erows)
-    assert np.array_equal(rows[:8 * k].reshape(k, 8), erows), (what, rows[:8 * k].reshape(k, 8), erows)
-    assert [int(v) for v in tot[:4]] == [zsfile.OVERFLOW if total > cap else 0, total, mx, mn], what
-    m = min(total, cap)
-    assert np.array_equal(off[:m], eoff[:m]) and np.array_equal(ln[:m], eln[:m]), what
-    assert np.array_equal(img[:m], eimg[:m]), what
-    # nothing at index >= min(total, cap) was written, nor past the rows and the totals
-    assert (off[m:] == CANARY_WORD).all() and (ln[m:] == CANARY_WORD).all(), what
-    assert (img[m:] == CANARY_WORD & 0xFFFFFFFF).all(), what
-    assert (rows[8 * k:] == CANARY_WORD).all() and (tot[4:] == CANARY_WORD).all(), what
-
-
 def _both(images, gaps=None, took_over=None, dev=None):
     buf, descs = _arena(images, gaps)
     return torch.from_numpy(buf).to(dev), descs, _expect(images, descs, took_over)
-
-
-def _finalised() -> bytes:
-    w = zf.FileWriter(UUID, idx=5)
-    for t in range(12):
-        w.add(b"f%04d" % t, b"q" * (t * 13))
-        w.commit()
-    w.finalise()
-    return w.image()
-
-
-def _key70k() -> bytes:
-    w = zf.FileWriter(UUID, idx=4)
-    w.add(b"a", b"b")
-    w.commit()
-    w.add(bytes(range(256)) * 273 + b"tail" * 28, b"value of the long key")
-    w.commit()
-    w.add(b"z", b"")
-    w.commit()
-    img = w.image()
-    assert len(img) > 70000
-    return img
 
 
 def _mixed(B: int, T: int):
@@ -379,13 +218,11 @@ def test_caller_scratch_fenced(gpu, mixed_default):
         d, descs, exp = _both(images, took_over=took, dev=gpu)
         need = zsfile.walk_multi_scratch_bytes(descs, block, tile)
         assert need > 0
-        whole = _canary(need + 2 * 4096, gpu)
-        scratch = whole[4096:4096 + need]
+        whole, scratch = dm.fenced(need, gpu)
         assert scratch.data_ptr() % 16 == 0
         mine = _run(d, descs, block=block, tile=tile, scratch=scratch)
         _check(mine, exp, ("caller scratch", block))
-        h = whole.cpu().numpy()
-        assert (h[:4096] == CANARY).all() and (h[4096 + need:] == CANARY).all()
+        assert dm.intact(whole, need)
         lib = _run(d, descs, block=block, tile=tile)
         assert all(np.array_equal(a, b) for a, b in zip(mine[:5], lib[:5]))
 
@@ -451,14 +288,6 @@ def _verify_equal(images, dev, gaps=None):
         if off % 8 == 0:
             assert got[j] == zsfile.verify_image(img, zsfile.ACTIVE), j
     return got
-
-
-def _stopped() -> bytes:
-    w = zf.FileWriter(UUID, idx=7)
-    for t in range(40):
-        w.add(b"s%05d" % t, b"u" * (t * 11))
-        w.commit(final=t == 25)
-    return w.image()
 
 
 def test_verify_images_equals_per_image(gpu):

@@ -39,9 +39,12 @@ import pytest
 import torch
 
 from oracle import zs_format as zf
+from tests import devmem as dm
 from tests import walk_images as wi
-from tests.test_format_oracle import UUID, build_active
-from tests.test_gpu_walk import CANARY, U64_MAX, _dev, _fenced, _intact, _same, _u64
+from tests.devmem import CANARY
+from tests.images import U64_MAX, UUID, build_active
+from tests.walk_images import dev_image as _dev
+from tests.walk_images import u64 as _u64
 from zeroskip_amd import zsfile
 from zeroskip_amd._lib import lib
 
@@ -105,11 +108,11 @@ def test_big_wellformed(gpu, big, d_big, block, tile):
     assert int(r[5]) == U64_MAX
     need = zsfile.walk_scratch_bytes(len(img), block, tile)
     assert need > 0
-    whole, scratch = _fenced(need, gpu)
+    whole, scratch = dm.fenced(need, gpu)
     assert scratch.data_ptr() % 16 == 0
     r = _equal(h, _walk(d_big, cap, block, tile, scratch=scratch), (block, tile, "caller scratch"))
     assert int(r[5]) == U64_MAX
-    assert _intact(whole, need)
+    assert dm.intact(whole, need)
 
 
 def test_big_serial_flag(gpu, big, d_big):
@@ -126,9 +129,9 @@ def test_big_cap(gpu, big, d_big):
     assert 1000 < c1 < n - 1000
     for cap in (n, n - 1, n + 1, 0, c1 - 1, c1, c1 + 1):
         room = max(cap, 1) * 8
-        fo, off = _fenced(room, gpu)
-        fl, ln = _fenced(room, gpu)
-        fr, res = _fenced(8 * zsfile.WALK_RES_WORDS, gpu)
+        fo, off = dm.fenced(room, gpu)
+        fl, ln = dm.fenced(room, gpu)
+        fr, res = dm.fenced(8 * zsfile.WALK_RES_WORDS, gpu)
         zsfile.device_walk(d_big, cap=cap, out=(off.view(torch.int64), ln.view(torch.int64), res.view(torch.int64)))
         r = _u64(res.view(torch.int64))
         assert int(r[0]) == (zsfile.OVERFLOW if cap < n else hrc), cap
@@ -139,7 +142,7 @@ def test_big_cap(gpu, big, d_big):
         assert np.array_equal(_u64(ln.view(torch.int64))[:k], hlen[:k]), cap
         # nothing at or beyond cap (or beyond the commits there are) is touched
         assert bool((off[k * 8:] == CANARY).all()) and bool((ln[k * 8:] == CANARY).all()), cap
-        assert _intact(fo, room) and _intact(fl, room) and _intact(fr, 8 * zsfile.WALK_RES_WORDS), cap
+        assert dm.intact(fo, room) and dm.intact(fl, room) and dm.intact(fr, 8 * zsfile.WALK_RES_WORDS), cap
 
 
 # ----------------------------------------------------------------------- fuzz

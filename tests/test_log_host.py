@@ -9,14 +9,14 @@ import os
 import numpy as np
 import pytest
 
-from oracle import zs_format as zf
 from tests import log_cases as lc
 from tests import records_images as ri
+from tests.images import REF as GOLDEN
+from tests.log_cases import check_against_image
 from zeroskip_amd import zsfile
 from zeroskip_amd._lib import lib
 
 CANARY = 0xA5
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_format")
 
 
 def run_host(case, slack=64, tile=0):
@@ -27,38 +27,6 @@ def run_host(case, slack=64, tile=0):
     d = zsfile.log(case.src, case.recs, case.tx_end, case.uuid, case.startidx, case.endidx, out=out, at=case.at,
                    finalise=case.finalise, prev_crc=case.prev_crc, tile_bytes=tile, new_recs=True, spans=True)
     return d, out
-
-
-def check_against_image(case, d, got: bytes):
-    """Image, words and optional outputs against the oracle's image and its listing."""
-    want = case.want
-    assert d["code"] == 0 and d["n"] == case.n and d["end"] == len(want), (case.name, d["code"], d["end"], len(want))
-    assert got[:len(want)] == want, case.name
-    assert d["written"] == len(want) - case.at and d["commits"] == case.n_commits
-    # what the lister and the walk find in the bytes written (the prefix cut off: offsets shifted back)
-    if case.at:
-        tail = zf.header_bytes(case.uuid, 0, 0) + want[case.at:]
-        shift = case.at - 40
-    else:
-        tail, shift = want, 0
-    recs, rc = ri.host_records(tail, zsfile.ACTIVE)
-    assert rc == zsfile.END and len(recs) == case.n, case.name
-    live = recs[:, 2] != lc.U64_MAX
-    recs[:, 0] += np.uint64(shift)
-    recs[live, 2] += np.uint64(shift)
-    assert np.array_equal(np.asarray(d["new_recs"]).view(np.uint64).reshape(-1, 4), recs), case.name
-    off, ln, rc, end = zsfile.walk(tail)
-    assert rc == zsfile.END and end == len(tail) and len(off) == case.n_commits, case.name
-    assert np.array_equal(np.asarray(d["span_off"]).view(np.uint64), off + np.uint64(shift)), case.name
-    assert np.array_equal(np.asarray(d["span_len"]).view(np.uint64), ln), case.name
-    assert d["long_commits"] == sum(1 for o, l in zip(off, ln) if tail[int(o + l)] == zf.REC_LONG_COMMIT)
-    assert d["last_crc"] == case.writer.mf_crc32, case.name
-    stored = int.from_bytes(want[-4:], "big") if case.n_commits else 0
-    assert d["stored_crc"] == stored, case.name
-    nc = case.n_commits
-    with np.errstate(over="ignore"):
-        bound = zsfile.device_log_bound(case.n, nc, int(case.recs[:, 1].sum()), int(case.recs[case.recs[:, 2] != lc.U64_MAX, 3].sum()))
-    assert bound + (case.at - 40 if case.at else 0) >= len(want), case.name
 
 
 def test_every_small_case():

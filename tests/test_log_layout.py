@@ -8,7 +8,6 @@ by a loop), at tile sizes 64, 128, 4096 and 65536 and grids of 1, 2, 7 and one
 more workgroup than tiles, and compares it with the format oracle's image.  The program is built with the address and
 undefined-behaviour sanitizers and runs as its own process; nothing is
 preloaded and nothing of it is loaded into python.  No GPU."""
-import os
 import re
 import struct
 import subprocess
@@ -16,24 +15,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import cprog
 from tests import log_cases as lc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "c", "log_layout.cpp")
 NO_TABLE = (1 << 64) - 1
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("log_layout") / "log_layout")
-    base = [os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", SRC, "-o", exe]
-    r = subprocess.run(base[:1] + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] + base[1:],
-                       capture_output=True, text=True)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        print("sanitizer build failed, building without:\n" + r.stderr[-2000:])
-        subprocess.run(base, check=True)
-    return exe, sanitized
+program = cprog.program_fixture("log_layout")
 
 
 def _run(program, tmp_path, case, shift, want=None):

@@ -7,30 +7,16 @@ and compares rows, seqs, cursors and result words with the Python model's.
 The program is built with the address and undefined-behaviour sanitizers and
 runs as its own process; nothing is preloaded and nothing of it is loaded into
 python.  No GPU."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cprog
 from tests import next_cases as nc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "c", "next_order.cpp")
 NO_COMPARE = nc.NO_COMPARE
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("next_order") / "next_order")
-    base = [os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", SRC, "-o", exe]
-    r = subprocess.run(base[:1] + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] + base[1:],
-                       capture_output=True, text=True)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        print("sanitizer build failed, building without:\n" + r.stderr[-2000:])
-        subprocess.run(base, check=True)
-    return exe, sanitized
+program = cprog.program_fixture("next_order")
 
 
 def _run(program, tmp_path, case, setting=(1, False, False, 0), shift=0, qshift=0, want=None):

@@ -8,30 +8,16 @@ advance, with the lanes played by a loop), at tile sizes 64, 128, 4096 and
 with the format oracle's file.  The program is
 built with the address and undefined-behaviour sanitizers and runs as its own
 process; nothing is preloaded and nothing of it is loaded into python.  No GPU."""
-import os
 import re
 import struct
 import subprocess
 
 import pytest
 
+from tests import cprog
 from tests import pack_cases as pc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "c", "pack_layout.cpp")
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("pack_layout") / "pack_layout")
-    base = [os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", SRC, "-o", exe]
-    r = subprocess.run(base[:1] + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] + base[1:],
-                       capture_output=True, text=True)
-    sanitized = r.returncode == 0
-    if not sanitized:
-        print("sanitizer build failed, building without:\n" + r.stderr[-2000:])
-        subprocess.run(base, check=True)
-    return exe, sanitized
+program = cprog.program_fixture("pack_layout")
 
 
 def _run(program, tmp_path, case, shift):

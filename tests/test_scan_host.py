@@ -10,11 +10,9 @@ import pytest
 
 from oracle import zs_format as zf
 from tests import scan_cases as sc
+from tests.images import REF, UUIDSTR
 from zeroskip_amd import repack, zsfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "tests", "golden", "ref_format")
-UUIDSTR = "00010203-0405-0607-0809-0a0b0c0d0e0f"
 U64 = np.uint64
 
 

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from tests import walk_images as wi
-from tests.test_format_oracle import build_active
+from tests.images import build_active
 from zeroskip_amd import zsfile
 
 

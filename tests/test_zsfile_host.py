@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from oracle import zs_format as zf
-from tests.test_format_oracle import UUID, build_active
+from tests.images import UUID, build_active
 from zeroskip_amd import zsfile
 
 
@@ -91,7 +91,7 @@ def test_record_lister_matches_oracle():
     pointer section (packed files, incl. a long value record); CPU only."""
     import numpy as np
     from oracle import zs_format as zf
-    from tests.test_format_oracle import UUID
+    from tests.images import UUID
     from zeroskip_amd import repack, zsfile
     rng = np.random.default_rng(31)
     w = zf.FileWriter(UUID, idx=4)

@@ -12,7 +12,7 @@ import numpy as np
 
 from oracle import zs_format as zf
 from tests import fuzzlib
-from tests.test_format_oracle import UUID, build_active
+from tests.images import UUID, build_active
 from zeroskip_amd import zsfile
 from zeroskip_amd._lib import lib
 
@@ -31,6 +31,35 @@ def host_walk(img):
     """zsfile.walk as uint64 arrays: (off, len, rc, end)."""
     off, ln, rc, end = zsfile.walk(img)
     return off.astype(np.uint64), ln.astype(np.uint64), rc, end
+
+
+def dev_image(img: bytes, dev):
+    """The image as a device tensor (torch is needed by the GPU tests only)."""
+    import torch
+    return torch.from_numpy(np.frombuffer(img, dtype=np.uint8).copy()).to(dev)
+
+
+def u64(t) -> np.ndarray:
+    return t.cpu().numpy().view(np.uint64)
+
+
+def device_walk(d, block=0, tile=0, serial=False):
+    off, ln, res = zsfile.device_walk(d, block_bytes=block, tile_bytes=tile, serial=serial)
+    r = u64(res)
+    n = int(r[1])
+    return u64(off[:n]), u64(ln[:n]), r
+
+
+def same_walk(img: bytes, d, block, tile, serial=False):
+    """The device walk of d equals the host walk of img; returns its res."""
+    hoff, hlen, hrc, hend = host_walk(img)
+    off, ln, r = device_walk(d, block, tile, serial)
+    what = (len(img), block, tile, serial)
+    assert (int(r[0]), int(r[1]), int(r[2])) == (hrc, len(hoff), hend), what
+    assert np.array_equal(off, hoff) and np.array_equal(ln, hlen), what
+    assert int(r[3]) == (int(hlen.max()) if len(hlen) else 0), what
+    assert int(r[4]) == (int(hlen.min()) if len(hlen) else 0), what
+    return r
 
 
 def host_walk_capped(img: np.ndarray, cap: int):
