@@ -188,3 +188,48 @@ def test_three_slots_region_spans_every_bound(gpu):
                 assert r["bad_commits"] == 1 and r["first_bad_file"] == 1 and r["first_bad_what"] == 3, (p, r)
     finally:
         zsfile.set_devices(None)
+
+
+def test_release_cache_frees_and_recovers(gpu):
+    """zscrc_release_cache() frees the per-slot cache of zscrc_zs_verify_files
+    and the next call allocates it again: three images of a few KiB (active,
+    finalised, packed) report the same before and after two releases, every
+    field but the three measured times.  That the device buffers went back is
+    read from the device's free memory, which moves only by whole blocks of a
+    few MiB; so, before it is read, one more call on a packed image of a few
+    MiB makes this cache alone hold more than that (its device image is the
+    size of the call's bytes), and the test holds in a process of its own."""
+    import torch
+    from zeroskip_amd._lib import lib
+    rng = np.random.default_rng(17)
+    w = zf.FileWriter(UUID, idx=1)
+    for t in range(12):
+        w.add(b"%016d" % t, rng.integers(0, 256, 300, dtype=np.uint8).tobytes())
+        w.commit()
+    w.finalise()
+    recs = sorted((b"%016d" % i, bytes(rng.integers(0, 256, 200, dtype=np.uint8))) for i in range(20))
+    imgs = [np.frombuffer(build_active(12), np.uint8).copy(),
+            np.frombuffer(w.image(), np.uint8).copy(),
+            np.frombuffer(zf.packed_file(recs, UUID, 0, 2), np.uint8).copy()]
+    kinds = [zsfile.ACTIVE, zsfile.FINALISED, zsfile.PACKED]
+    assert all(2048 < im.nbytes < 16384 for im in imgs)
+    first = zsfile.verify_files(imgs, kinds, threads=2)
+    commits, bad, stale = _expected(imgs, kinds)
+    assert first["commits"] == commits and first["bad_commits"] == bad == 0
+    assert first["stale_empty_commits"] == stale == 1 and first["first_bad_what"] == 0
+    big = sorted((b"%016d" % i, bytes(rng.integers(0, 256, 8000, dtype=np.uint8))) for i in range(1000))
+    big = np.frombuffer(zf.packed_file(big, UUID, 0, 2), np.uint8).copy()
+    assert 6 << 20 < big.nbytes < 10 << 20
+    rep = zsfile.verify_files([big], [zsfile.PACKED], threads=2)
+    assert rep["commits"] == 2 and rep["bad_commits"] == 0 and rep["first_bad_what"] == 0
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    lib().zscrc_release_cache()
+    free1 = torch.cuda.mem_get_info()[0]
+    print("free device memory before and after the release:", free0, free1)
+    assert free1 > free0   # device buffers went back
+    lib().zscrc_release_cache()   # twice is harmless
+    again = zsfile.verify_files(imgs, kinds, threads=2)
+    timed = {"copy_s", "verify_tail_s", "total_s"}
+    assert set(again) == set(first) and timed < set(first)
+    assert {k: v for k, v in again.items() if k not in timed} == {k: v for k, v in first.items() if k not in timed}

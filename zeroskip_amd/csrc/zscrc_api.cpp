@@ -129,22 +129,16 @@ struct DevCtx {
     std::recursive_mutex mu;
     bool ready = false;
     int ncu = 0;
-    uint32_t *gtab = nullptr;
-    uint32_t *sink = nullptr;  /* 4 KiB a kernel's masked-off stores go to */
-    void *scratch = nullptr;   /* span partials */
-    size_t scratch_bytes = 0;
-    void *stage = nullptr;     /* host-batch staging */
-    size_t stage_bytes = 0;
-    void *classes = nullptr;   /* class lists + counters of variable batches */
-    size_t classes_bytes = 0;
-    void *parts = nullptr;     /* part registers of split long records */
-    void *qparts = nullptr;    /* qteam_dyn_kernel: part registers */
-    size_t qparts_bytes = 0;
-    void *rlist = nullptr;     /* split commit batches: leftover-round count + list */
-    size_t rlist_bytes = 0;
-    void *wbuf = nullptr;      /* two-pass commit writer: statuses (+ CRCs) */
-    size_t wbuf_bytes = 0;
-    size_t parts_bytes = 0;
+    zs::DevBuf tab;            /* the operator tables: gtab() */
+    zs::DevBuf sink;           /* 4 KiB a kernel's masked-off stores go to */
+    zs::DevBuf scratch;        /* span partials */
+    zs::DevBuf stage;          /* host-batch staging */
+    zs::DevBuf classes;        /* class lists + counters of variable batches */
+    zs::DevBuf parts;          /* part registers of split long records */
+    zs::DevBuf qparts;         /* qteam_dyn_kernel: part registers */
+    zs::DevBuf rlist;          /* split commit batches: leftover-round count + list */
+    zs::DevBuf wbuf;           /* two-pass commit writer: statuses (+ CRCs) */
+    const uint32_t *gtab() const { return tab.as<uint32_t>(); }
     hipEvent_t last = nullptr; /* end of the last scratch user's work ... */
     hipStream_t last_stream = nullptr; /* ... enqueued on this stream */
     bool last_valid = false;
@@ -152,11 +146,11 @@ struct DevCtx {
      * (count, workgroups done) pairs per stream that used one, 0 at rest --
      * calls on one stream are ordered, so a stream's own pair needs no
      * event (verdict_slot) */
-    unsigned long long *vctr = nullptr;
+    zs::DevBuf vctr;
     /* class-3-only verdicts (xteam_kernel MODE 3 + nbv_fold_kernel): part
      * registers per segment, then the commits' starts; used under the
      * scratch's cross-stream ordering */
-    uint32_t *nbv = nullptr;
+    zs::DevBuf nbv;
     hipStream_t vctr_stream[64] = {};
     uint32_t vctr_turn[64] = {};
     int vctr_n = 0;
@@ -263,19 +257,17 @@ int get_ctx(DevCtx **out)
     static uint32_t host_tab[GT_WORDS];
     static std::once_flag tab_once;
     std::call_once(tab_once, [] { build_gtab(host_tab); });
-    e = hipMalloc(&c.gtab, sizeof host_tab);
-    if (e != hipSuccess) {
-        set_err("hipMalloc(tables)", e);
+    if (c.tab.reserve(sizeof host_tab)) {
+        set_err("hipMalloc(tables)", (hipError_t)c.tab.error());
         return ZSCRC_ENOMEM;
     }
-    e = hipMemcpy(c.gtab, host_tab, sizeof host_tab, hipMemcpyHostToDevice);
+    e = hipMemcpy(c.tab.as<void>(), host_tab, sizeof host_tab, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         set_err("hipMemcpy(tables)", e);
         return ZSCRC_EHIP;
     }
-    e = hipMalloc(&c.sink, 4096);
-    if (e != hipSuccess) {
-        set_err("hipMalloc(sink)", e);
+    if (c.sink.reserve(4096)) {
+        set_err("hipMalloc(sink)", (hipError_t)c.sink.error());
         return ZSCRC_ENOMEM;
     }
     c.ncu = ncu;
@@ -285,22 +277,13 @@ int get_ctx(DevCtx **out)
     return ZSCRC_OK;
 }
 
-int grow(void **p, size_t *have, size_t need)
+/* A context buffer grown to `need` bytes and a quarter more. */
+int grow(zs::DevBuf &b, size_t need)
 {
-    if (*have >= need)
-        return ZSCRC_OK;
-    if (*p)
-        (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    size_t n = need + need / 4;
-    hipError_t e = hipMalloc(p, n);
-    if (e != hipSuccess) {
-        set_err("hipMalloc(scratch)", e);
-        return ZSCRC_ENOMEM;
-    }
-    *have = n;
-    return ZSCRC_OK;
+    const int rc = b.reserve(need, need / 4);
+    if (rc)
+        set_err("hipMalloc(scratch)", (hipError_t)b.error());
+    return rc;
 }
 
 /* The scratch buffers (class lists, part registers, span partials) are
@@ -479,7 +462,7 @@ int launch_qdyn(DevCtx *c, const zs::BatchDesc &d, hipStream_t s)
         q.lds_fold = 1;
         q.K = K;
         q.K_last = K_last;
-        if (zs_launch_qdyn(&d, &q, K, K_last, c->gtab, c->ncu, s)) {
+        if (zs_launch_qdyn(&d, &q, K, K_last, c->gtab(), c->ncu, s)) {
             set_err("qteam dyn launch", hipGetLastError());
             return ZSCRC_EHIP;
         }
@@ -490,14 +473,14 @@ int launch_qdyn(DevCtx *c, const zs::BatchDesc &d, hipStream_t s)
     int rc = scratch_acquire(c, s);
     if (rc)
         return rc;
-    rc = grow(&c->qparts, &c->qparts_bytes, (size_t)d.n * np * sizeof(uint32_t));
+    rc = grow(c->qparts, (size_t)d.n * np * sizeof(uint32_t));
     if (!rc) {
         zs::QDyn q;
         memset(&q, 0, sizeof q);
-        q.part_out = static_cast<uint32_t *>(c->qparts);
+        q.part_out = c->qparts.as<uint32_t>();
         q.P = P;
         q.np = np;
-        if (zs_launch_qdyn(&d, &q, K, K_last, c->gtab, c->ncu, s)) {
+        if (zs_launch_qdyn(&d, &q, K, K_last, c->gtab(), c->ncu, s)) {
             set_err("qteam dyn launch", hipGetLastError());
             rc = ZSCRC_EHIP;
         } else {
@@ -529,11 +512,11 @@ int launch(DevCtx *c, int g, const zs::BatchDesc &d, hipStream_t s, int depth_hi
     const bool qteam = g == 16 && fixed && g_qteam && g_depth[1] < 0 && depth_hint < 0 && qteam_fits(d);
     if (qteam && qdeal_for(c, d))
         return launch_qdyn(c, d, s);
-    int rc = qteam       ? zs_launch_xteam(16, &d, c->gtab, c->ncu, s)
-             : xteam     ? zs_launch_xteam(xt, &d, c->gtab, c->ncu, s)
-             : depth >= 9 ? zs_launch_burst(fixed, depth == 10, nb, &dx, c->gtab, c->ncu, s)
-             : depth >= 3 ? zs_launch_short(fixed, depth - 3, &dx, c->gtab, c->ncu, s)
-                        : zs_launch_team(g, fixed, depth, &d, c->gtab, c->ncu, s);
+    int rc = qteam       ? zs_launch_xteam(16, &d, c->gtab(), c->ncu, s)
+             : xteam     ? zs_launch_xteam(xt, &d, c->gtab(), c->ncu, s)
+             : depth >= 9 ? zs_launch_burst(fixed, depth == 10, nb, &dx, c->gtab(), c->ncu, s)
+             : depth >= 3 ? zs_launch_short(fixed, depth - 3, &dx, c->gtab(), c->ncu, s)
+                        : zs_launch_team(g, fixed, depth, &d, c->gtab(), c->ncu, s);
     if (rc) {
         set_err("team kernel launch", hipGetLastError());
         return ZSCRC_EHIP;
@@ -572,7 +555,7 @@ int launch_commit(DevCtx *c, zs::BatchDesc d, hipStream_t s)
         return launch_commit_two_pass(c, d, s);
     if (!split || !(d.opt & zs::OPT_RO_LIST)) {
         d.round_mode = split ? 3 : 0;
-        if (zs_launch_commit(&d, c->gtab, c->ncu, s)) {
+        if (zs_launch_commit(&d, c->gtab(), c->ncu, s)) {
             set_err("commit kernel launch", hipGetLastError());
             return ZSCRC_EHIP;
         }
@@ -582,9 +565,9 @@ int launch_commit(DevCtx *c, zs::BatchDesc d, hipStream_t s)
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     int rc = scratch_acquire(c, s);
     if (!rc)
-        rc = grow(&c->rlist, &c->rlist_bytes, 4 * (nr + 1));
+        rc = grow(c->rlist, 4 * (nr + 1));
     if (!rc) {
-        uint32_t *cnt = static_cast<uint32_t *>(c->rlist);
+        uint32_t *cnt = c->rlist.as<uint32_t>();
         hipError_t e = hipMemsetAsync(cnt, 0, sizeof(uint32_t), s);
         if (e != hipSuccess) {
             set_err("hipMemsetAsync(round count)", e);
@@ -594,7 +577,7 @@ int launch_commit(DevCtx *c, zs::BatchDesc d, hipStream_t s)
         d.round_list = cnt + 1;
         for (int mode = 1; !rc && mode <= 2; ++mode) {
             d.round_mode = mode;
-            if (zs_launch_commit(&d, c->gtab, c->ncu, s)) {
+            if (zs_launch_commit(&d, c->gtab(), c->ncu, s)) {
                 set_err("commit kernel launch", hipGetLastError());
                 rc = ZSCRC_EHIP;
             } else {
@@ -619,9 +602,9 @@ int launch_commit_two_pass(DevCtx *c, zs::BatchDesc d, hipStream_t s)
     int rc = scratch_acquire(c, s);
     const size_t n = d.n;
     if (!rc)
-        rc = grow(&c->wbuf, &c->wbuf_bytes, (d.out ? 4 : 8) * n);
+        rc = grow(c->wbuf, (d.out ? 4 : 8) * n);
     if (!rc) {
-        uint32_t *st = static_cast<uint32_t *>(c->wbuf);
+        uint32_t *st = c->wbuf.as<uint32_t>();
         uint32_t *crc = d.out ? d.out : st + n;
         uint32_t *user_status = d.status;
         zs::BatchDesc dc = d;
@@ -629,7 +612,7 @@ int launch_commit_two_pass(DevCtx *c, zs::BatchDesc d, hipStream_t s)
         dc.out = crc;
         dc.status = st;
         dc.round_mode = 3;
-        if (zs_launch_commit(&dc, c->gtab, c->ncu, s) ||
+        if (zs_launch_commit(&dc, c->gtab(), c->ncu, s) ||
             zs_launch_commit_scatter(const_cast<uint8_t *>(d.base), d.off, d.len, crc, st, n, user_status, c->ncu,
                                      s)) {
             set_err("commit writer launch", hipGetLastError());
@@ -662,17 +645,16 @@ unsigned long long *verdict_slot(DevCtx *c, hipStream_t s)
     if (s == hipStreamLegacy) /* the NULL stream under another name */
         s = nullptr;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (!c->vctr) {
+    if (!c->vctr.bytes()) {
         /* every pair zeroed here, before any stream can use one (the pairs
          * are 0 at rest, so nothing is zeroed per stream afterwards) */
-        void *p = nullptr;
-        if (hipMalloc(&p, 64 * 4 * 128) != hipSuccess)
+        if (c->vctr.reserve(64 * 4 * 128))
             return nullptr;
-        if (hipMemset(p, 0, 64 * 4 * 128) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
-            (void)hipFree(p);
+        if (hipMemset(c->vctr.as<void>(), 0, 64 * 4 * 128) != hipSuccess ||
+            hipStreamSynchronize(nullptr) != hipSuccess) {
+            c->vctr.release();
             return nullptr;
         }
-        c->vctr = static_cast<unsigned long long *>(p);
     }
     int k = 0;
     while (k < c->vctr_n && c->vctr_stream[k] != s)
@@ -683,7 +665,7 @@ unsigned long long *verdict_slot(DevCtx *c, hipStream_t s)
         c->vctr_stream[c->vctr_n++] = s;
     }
     const uint32_t turn = c->vctr_turn[k]++ & 3;
-    return c->vctr + 16 * (4 * k + turn);
+    return c->vctr.as<unsigned long long>() + 16 * (4 * k + turn);
 }
 
 /* max_len: a bound on the lengths -- at most g1_max, one kernel straight
@@ -776,16 +758,16 @@ int launch_classes_locked(DevCtx *c, zs::BatchDesc d, hipStream_t s, uint64_t g1
      * segment plan: rec_start (< T records, 64-bit) and seg_first (nseg3 + 1) */
     const size_t part_bytes = (5 * T + 2 * P3 + T + 2 * T + nseg3 + 64) * sizeof(uint32_t);
     {
-        int rc = grow(&c->classes, &c->classes_bytes, list_bytes);
+        int rc = grow(c->classes, list_bytes);
         if (!rc)
-            rc = grow(&c->parts, &c->parts_bytes, part_bytes);
+            rc = grow(c->parts, part_bytes);
         if (rc)
             return rc;
     }
-    uint32_t *cnt = static_cast<uint32_t *>(c->classes);
-    uint64_t *cbytes = reinterpret_cast<uint64_t *>(static_cast<char *>(c->classes) + 32);
-    zs::SplitPlan *plans = reinterpret_cast<zs::SplitPlan *>(static_cast<char *>(c->classes) + 64);
-    zs::RecDesc *desc = reinterpret_cast<zs::RecDesc *>(static_cast<char *>(c->classes) + HEAD);
+    uint32_t *cnt = c->classes.as<uint32_t>();
+    uint64_t *cbytes = reinterpret_cast<uint64_t *>(c->classes.as<char>() + 32);
+    zs::SplitPlan *plans = reinterpret_cast<zs::SplitPlan *>(c->classes.as<char>() + 64);
+    zs::RecDesc *desc = reinterpret_cast<zs::RecDesc *>(c->classes.as<char>() + HEAD);
     const int team[4] = {1, 16, 16, gs};
     const int walk[4] = {-1, 1, 0, 0};
     /* classes 2-3 with fewer records than two per team are cut into equal
@@ -808,10 +790,10 @@ int launch_classes_locked(DevCtx *c, zs::BatchDesc d, hipStream_t s, uint64_t g1
             p.target *= 2; /* four parts per wave (A/B) */
         p.unit_min = (uint64_t)team[k] * 64 * 16; /* 16 steps of the team */
         p.always_split = k == 3 && xparts ? 1u : 0u;
-        p.gtab = c->gtab;
+        p.gtab = c->gtab();
         p.plan = plans;
         const size_t cap = k == 3 ? P3 : 2 * T;
-        part_out[k - 2] = static_cast<uint32_t *>(c->parts) + (k == 3 ? 5 * T : 0);
+        part_out[k - 2] = c->parts.as<uint32_t>() + (k == 3 ? 5 * T : 0);
         p.part_rec = part_out[k - 2] + cap;
         p.part_base = p.part_rec + cap;
         if (k == 3 && xseg) {
@@ -893,17 +875,10 @@ int launch_classes_locked(DevCtx *c, zs::BatchDesc d, hipStream_t s, uint64_t g1
         pa[1].nseg == nseg3 && nseg3 == (size_t)c->ncu * 16 && nbv_parts_fit()) {
         unsigned long long *pair = verdict_slot(c, s);
         if (pair) {
-            if (!c->nbv) {
-                void *p = nullptr;
-                const size_t bytes = 2 * nseg3 * sizeof(uint32_t) + (zs::NBV_MAX + 1) * sizeof(uint64_t);
-                hipError_t e = hipMalloc(&p, bytes);
-                if (e != hipSuccess) {
-                    if (p)
-                        (void)hipFree(p);
-                    set_err("nbv buffers", e);
-                    return ZSCRC_EHIP;
-                }
-                c->nbv = static_cast<uint32_t *>(p);
+            /* nseg3 is the device's: allocated once */
+            if (c->nbv.reserve(2 * nseg3 * sizeof(uint32_t) + (zs::NBV_MAX + 1) * sizeof(uint64_t))) {
+                set_err("nbv buffers", (hipError_t)c->nbv.error());
+                return ZSCRC_EHIP;
             }
             zs::XParts x;
             memset(&x, 0, sizeof x);
@@ -914,15 +889,15 @@ int launch_classes_locked(DevCtx *c, zs::BatchDesc d, hipStream_t s, uint64_t g1
             x.seed3 = d.seed;
             x.n3 = n;
             x.img_size = d.img_size;
-            x.nbv = c->nbv;
-            x.rstart = reinterpret_cast<uint64_t *>(c->nbv + 2 * nseg3);
+            x.nbv = c->nbv.as<uint32_t>();
+            x.rstart = reinterpret_cast<uint64_t *>(x.nbv + 2 * nseg3);
             x.vpair = pair;
             x.publish = d.bad_count;
             x.bad_idx = d.bad_idx;
             x.bad_cap = d.bad_cap;
             x.nseg = (uint32_t)nseg3;
             x.unit_min = pa[1].unit_min;
-            if (zs_launch_nbv(&x, c->gtab, c->ncu, s)) {
+            if (zs_launch_nbv(&x, c->gtab(), c->ncu, s)) {
                 set_err("nbv launch", hipGetLastError());
                 return ZSCRC_EHIP;
             }
@@ -987,7 +962,7 @@ int launch_classes_locked(DevCtx *c, zs::BatchDesc d, hipStream_t s, uint64_t g1
         }
         int rc;
         if (k == 3 && xparts) {
-            rc = zs_launch_xparts(&dk, c->gtab, c->ncu, xdeal != 0, s) ? ZSCRC_EHIP : ZSCRC_OK;
+            rc = zs_launch_xparts(&dk, c->gtab(), c->ncu, xdeal != 0, s) ? ZSCRC_EHIP : ZSCRC_OK;
             if (rc)
                 set_err("xparts launch", hipGetLastError());
             else
@@ -1002,7 +977,7 @@ int launch_classes_locked(DevCtx *c, zs::BatchDesc d, hipStream_t s, uint64_t g1
     }
     /* both split classes' folds in one launch */
     if (nfold) {
-        if (zs_launch_part_fold(fold, nfold, c->gtab, s)) {
+        if (zs_launch_part_fold(fold, nfold, c->gtab(), s)) {
             set_err("part fold launch", hipGetLastError());
             return ZSCRC_EHIP;
         }
@@ -1045,10 +1020,10 @@ int span_impl(DevCtx *c, const void *d_buf, uint64_t len, uint32_t seed, uint32_
     const uint64_t w = (len + seg - 1) / seg;
     uint32_t *part = static_cast<uint32_t *>(scratch);
     if (!part) {
-        int rc = grow(&c->scratch, &c->scratch_bytes, w * 4);
+        int rc = grow(c->scratch, w * 4);
         if (rc)
             return rc;
-        part = static_cast<uint32_t *>(c->scratch);
+        part = c->scratch.as<uint32_t>();
     }
     d.base = static_cast<const uint8_t *>(d_buf);
     d.n = w;
@@ -1061,7 +1036,7 @@ int span_impl(DevCtx *c, const void *d_buf, uint64_t len, uint32_t seed, uint32_
     int rc;
     if (deal) { /* the segments are shorter than launch()'s xteam bound */
         d.opt |= zs::OPT_XDEAL;
-        rc = zs_launch_xteam(g_xteam, &d, c->gtab, c->ncu, s) ? ZSCRC_EHIP : ZSCRC_OK;
+        rc = zs_launch_xteam(g_xteam, &d, c->gtab(), c->ncu, s) ? ZSCRC_EHIP : ZSCRC_OK;
         if (rc)
             set_err("span launch", hipGetLastError());
         else
@@ -1092,7 +1067,7 @@ int span_impl(DevCtx *c, const void *d_buf, uint64_t len, uint32_t seed, uint32_
         set_err("hipMemsetD32Async(span result)", e);
         return ZSCRC_EHIP;
     }
-    if (zs_launch_span_fold(&f, c->gtab, s)) {
+    if (zs_launch_span_fold(&f, c->gtab(), s)) {
         set_err("span fold launch", hipGetLastError());
         return ZSCRC_EHIP;
     }
@@ -1312,12 +1287,12 @@ int zscrc_device_fixed_multi(const void *const *d_bases, uint32_t *const *d_outs
     zs::MultiBatch m;
     memset(&m, 0, sizeof m);
     m.nb = (uint32_t)k;
-    m.sink = c->sink;
+    m.sink = c->sink.as<uint32_t>();
     for (size_t b = 0; b < k; ++b) {
         m.base[b] = static_cast<const uint8_t *>(d_bases[b]);
         m.out[b] = d_outs[b];
     }
-    if (zs_launch_multi(&d, &m, c->gtab, c->ncu, s)) {
+    if (zs_launch_multi(&d, &m, c->gtab(), c->ncu, s)) {
         set_err("multi kernel launch", hipGetLastError());
         return ZSCRC_EHIP;
     }
@@ -1432,9 +1407,9 @@ static int device_spans(const void *const *d_bufs, const uint64_t *lens, const u
     if (!part_own && (rc = scratch_acquire(c, s)))
         return rc;
     if (!part_own)
-        rc = grow(&c->scratch, &c->scratch_bytes, w * 4);
+        rc = grow(c->scratch, w * 4);
     if (!rc) {
-        uint32_t *part = part_own ? part_own : static_cast<uint32_t *>(c->scratch);
+        uint32_t *part = part_own ? part_own : c->scratch.as<uint32_t>();
         const uint32_t kseg = zs_gf2_xpow8n(seg);
         for (size_t i = 0; i < k; ++i) {
             zs::SpanFold &f = fs.f[i];
@@ -1461,7 +1436,7 @@ static int device_spans(const void *const *d_bufs, const uint64_t *lens, const u
         x.last_len = seg;
         if (defer_folds) /* the caller's kernel folds them (zscrc_cpass's post kernel) */
             *defer_folds = fs;
-        if (zs_launch_spans(&x, &m, defer_folds ? nullptr : &fs, c->gtab, c->ncu, deal != 0, s)) {
+        if (zs_launch_spans(&x, &m, defer_folds ? nullptr : &fs, c->gtab(), c->ncu, deal != 0, s)) {
             set_err("multi-span launch", hipGetLastError());
             rc = ZSCRC_EHIP;
         } else {
@@ -1542,9 +1517,9 @@ int zscrc_host_batch(const void *base, const uint64_t *off, const uint64_t *len,
     const uint64_t data = (hi - lo + 15) & ~15ull;
     const uint64_t need = data + n * (8 + 8 + 4 + 4) + 64;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if ((rc = grow(&c->stage, &c->stage_bytes, need)))
+    if ((rc = grow(c->stage, need)))
         return rc;
-    uint8_t *dbase = static_cast<uint8_t *>(c->stage);
+    uint8_t *dbase = c->stage.as<uint8_t>();
     uint64_t *doff = reinterpret_cast<uint64_t *>(dbase + data);
     uint64_t *dlen = doff + n;
     uint32_t *dseed = reinterpret_cast<uint32_t *>(dlen + n);
@@ -1891,7 +1866,7 @@ void zscrc_set_teams(uint64_t g1_max, uint64_t g16_max)
 const uint32_t *zscrc_internal_gtab(void)
 {
     DevCtx *c;
-    return get_ctx(&c) ? nullptr : c->gtab;
+    return get_ctx(&c) ? nullptr : c->gtab();
 }
 
 int zscrc_abi_version(void)
@@ -1931,13 +1906,11 @@ struct zscrc_stream {
     hipStream_t cs = nullptr, ks = nullptr; /* copy / compute */
     uint32_t seed = 0;
     uint64_t chunk = 0;
-    uint8_t *dbuf[NSLOT] = {};
-    uint8_t *hpin[NSLOT] = {};
-    void *scr[NSLOT] = {};
+    zs::DevBuf dbuf[NSLOT], scr[NSLOT];
+    zs::PinBuf hpin[NSLOT];
     hipEvent_t copied[NSLOT] = {}, done[NSLOT] = {};
     bool used[NSLOT] = {};
-    uint32_t *dparts = nullptr;
-    size_t cap = 0;
+    zs::DevBuf dparts; /* the chunks' raw registers */
     std::vector<uint64_t> lens;
     int slot = 0;
     uint64_t fill = 0;   /* copy mode: bytes staged in hpin[slot] */
@@ -1961,32 +1934,30 @@ int stream_submit(zscrc_stream *s, const void *src, uint64_t n)
     const int k = s->slot;
     const size_t idx = s->lens.size();
     hipError_t e;
-    if (idx >= s->cap) {
-        /* grow the device register array (rare: doubles) */
-        size_t ncap = s->cap ? 2 * s->cap : 4096;
-        uint32_t *np = nullptr;
+    if (const size_t cap = s->dparts.bytes() / 4; idx >= cap) {
+        /* grow the device register array (rare: doubles), keeping its contents:
+         * the old one is freed at the end of this block, after the copy */
+        zs::ScopedBuf<zs::Device> next;
         if ((e = hipStreamSynchronize(s->ks)) != hipSuccess)
             return stream_fail(s, "hipStreamSynchronize", e);
-        if ((e = hipMalloc(&np, ncap * 4)) != hipSuccess)
-            return stream_fail(s, "hipMalloc(stream registers)", e);
-        if (s->dparts) {
-            (void)hipMemcpy(np, s->dparts, s->cap * 4, hipMemcpyDeviceToDevice);
-            (void)hipFree(s->dparts);
-        }
-        s->dparts = np;
-        s->cap = ncap;
+        if (next.reserve((cap ? 2 * cap : 4096) * 4))
+            return stream_fail(s, "hipMalloc(stream registers)", (hipError_t)next.error());
+        if (cap)
+            (void)hipMemcpy(next.as<void>(), s->dparts.as<void>(), cap * 4, hipMemcpyDeviceToDevice);
+        next.swap(s->dparts);
     }
     /* the slot's device buffer is free once its previous CRC finished */
     if (s->used[k] && (e = hipStreamWaitEvent(s->cs, s->done[k], 0)) != hipSuccess)
         return stream_fail(s, "hipStreamWaitEvent", e);
-    if ((e = hipMemcpyAsync(s->dbuf[k], src, n, hipMemcpyHostToDevice, s->cs)) != hipSuccess)
+    if ((e = hipMemcpyAsync(s->dbuf[k].as<void>(), src, n, hipMemcpyHostToDevice, s->cs)) != hipSuccess)
         return stream_fail(s, "hipMemcpyAsync H2D", e);
     if ((e = hipEventRecord(s->copied[k], s->cs)) != hipSuccess ||
         (e = hipStreamWaitEvent(s->ks, s->copied[k], 0)) != hipSuccess)
         return stream_fail(s, "stream event", e);
     {
         std::lock_guard<std::recursive_mutex> lk(s->c->mu);
-        int rc = span_impl(s->c, s->dbuf[k], n, 0, s->dparts + idx, s->scr[k], ZSCRC_RAW, s->ks);
+        int rc = span_impl(s->c, s->dbuf[k].as<void>(), n, 0, s->dparts.as<uint32_t>() + idx, s->scr[k].as<void>(), ZSCRC_RAW,
+                           s->ks);
         if (rc)
             return s->err = rc;
     }
@@ -2007,19 +1978,15 @@ void stream_free(zscrc_stream *s)
     if (s->ks)
         (void)hipStreamSynchronize(s->ks);
     for (int k = 0; k < zscrc_stream::NSLOT; ++k) {
-        if (s->dbuf[k])
-            (void)hipFree(s->dbuf[k]);
-        if (s->scr[k])
-            (void)hipFree(s->scr[k]);
-        if (s->hpin[k])
-            (void)hipHostFree(s->hpin[k]);
+        s->dbuf[k].release();
+        s->scr[k].release();
+        s->hpin[k].release();
         if (s->copied[k])
             (void)hipEventDestroy(s->copied[k]);
         if (s->done[k])
             (void)hipEventDestroy(s->done[k]);
     }
-    if (s->dparts)
-        (void)hipFree(s->dparts);
+    s->dparts.release();
     if (s->cs)
         (void)hipStreamDestroy(s->cs);
     if (s->ks)
@@ -2053,11 +2020,11 @@ int zscrc_stream_open(zscrc_stream **out, uint32_t seed, uint64_t chunk_bytes, u
     if (e == hipSuccess)
         e = hipStreamCreateWithFlags(&s->ks, hipStreamNonBlocking);
     for (int k = 0; e == hipSuccess && k < zscrc_stream::NSLOT; ++k) {
-        e = hipMalloc(&s->dbuf[k], s->chunk);
+        e = zs::reserve_hip(s->dbuf[k], s->chunk);
         if (e == hipSuccess)
-            e = hipMalloc(&s->scr[k], zscrc_span_scratch_bytes(s->chunk));
+            e = zs::reserve_hip(s->scr[k], zscrc_span_scratch_bytes(s->chunk));
         if (e == hipSuccess && !(flags & ZSCRC_STREAM_NOCOPY))
-            e = hipHostMalloc(reinterpret_cast<void **>(&s->hpin[k]), s->chunk, hipHostMallocDefault);
+            e = zs::reserve_hip(s->hpin[k], s->chunk);
         if (e == hipSuccess)
             e = hipEventCreateWithFlags(&s->copied[k], hipEventDisableTiming);
         if (e == hipSuccess)
@@ -2101,13 +2068,13 @@ int zscrc_stream_update(zscrc_stream *s, const void *buf, size_t len)
                 return stream_fail(s, "hipEventSynchronize", e);
         }
         const uint64_t n = len < s->chunk - s->fill ? len : s->chunk - s->fill;
-        memcpy(s->hpin[k] + s->fill, p, n);
+        memcpy(s->hpin[k].as<uint8_t>() + s->fill, p, n);
         s->fill += n;
         p += n;
         len -= n;
         if (s->fill == s->chunk) {
             s->fill = 0;
-            int rc = stream_submit(s, s->hpin[k], s->chunk);
+            int rc = stream_submit(s, s->hpin[k].as<uint8_t>(), s->chunk);
             if (rc)
                 return rc;
         }
@@ -2135,7 +2102,7 @@ uint8_t *zscrc_internal_stream_stage(zscrc_stream *s, uint64_t *room)
         }
     }
     *room = s->chunk - s->fill;
-    return s->hpin[k] + s->fill;
+    return s->hpin[k].as<uint8_t>() + s->fill;
 }
 
 int zscrc_internal_stream_advance(zscrc_stream *s, uint64_t n, int flush, const uint8_t **done, uint64_t *done_n)
@@ -2151,10 +2118,10 @@ int zscrc_internal_stream_advance(zscrc_stream *s, uint64_t n, int flush, const 
         const int k = s->slot;
         const uint64_t m = s->fill;
         s->fill = 0;
-        int rc = stream_submit(s, s->hpin[k], m);
+        int rc = stream_submit(s, s->hpin[k].as<uint8_t>(), m);
         if (rc)
             return rc;
-        *done = s->hpin[k];
+        *done = s->hpin[k].as<uint8_t>();
         *done_n = m;
     }
     return ZSCRC_OK;
@@ -2172,13 +2139,13 @@ int stream_collect(zscrc_stream *s, uint32_t *crc)
     if (!rc && s->fill) {
         const uint64_t n = s->fill;
         s->fill = 0;
-        rc = stream_submit(s, s->hpin[s->slot], n);
+        rc = stream_submit(s, s->hpin[s->slot].as<uint8_t>(), n);
     }
     std::vector<uint32_t> raw(s->lens.size());
     if (!rc && !raw.empty()) {
         hipError_t e = hipStreamSynchronize(s->ks);
         if (e == hipSuccess)
-            e = hipMemcpy(raw.data(), s->dparts, raw.size() * 4, hipMemcpyDeviceToHost);
+            e = hipMemcpy(raw.data(), s->dparts.as<void>(), raw.size() * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess)
             rc = stream_fail(s, "stream final", e);
     }

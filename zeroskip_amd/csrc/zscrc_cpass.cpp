@@ -56,9 +56,9 @@ struct zscrc_cpass {
      * kernel zeroes the other block's counters for the next pass, so no
      * memset launch precedes a pass (two fill kernels of ~4.5 us and their
      * gaps per pass until then) */
-    uint8_t *dblk = nullptr;   /* 2 x BLK */
+    zs::DevBuf dblk;           /* 2 x BLK */
     int blk_next = 0;
-    uint8_t *hblk = nullptr;   /* NSLOT host blocks (zscrc_cpass_submit / _collect) */
+    zs::PinBuf hblk;           /* NSLOT host blocks (zscrc_cpass_submit / _collect) */
     hipEvent_t done[2] = {};   /* each slot's completion */
     /* passes in stream order (the blocks' counters are zeroed by the
      * previous pass): a pass enqueued on another stream than the previous
@@ -73,15 +73,16 @@ struct zscrc_cpass {
     /* the digest row (zscrc_cpass_set_row / _submit_row) */
     bool have_row = false;
     zs::CPassRowArgs row = {};
-    int64_t *dpiece = nullptr;
-    uint64_t *dbad_full = nullptr; /* the verdict's list (cap entries) */
+    zs::DevBuf dpiece;
+    zs::DevBuf dbad_full;      /* the verdict's list (cap entries) */
     uint64_t cap = 0;
+    zs::DevBuf dspan;          /* span_commit (int64), then span_init (uint32), CPASS_SPANS each */
     int64_t *dspan_commit = nullptr;
     uint32_t *dspan_init = nullptr;
     /* the multi-span launches' segment registers: the handle's own, so a
      * pass needs no ordering event on the device's shared scratch (its
      * record put ~6 us between the folds and the post kernel) */
-    uint32_t *dpart = nullptr;
+    zs::DevBuf dpart;
     uint64_t part_words = 0;
     /* one stream: the raw spans on a second stream beside the verdict batch
      * measured slower (config 5: 1.659 vs 1.542 ms per pass,
@@ -109,18 +110,12 @@ void cpass_free(zscrc_cpass *p)
         }
     if (p->order)
         (void)hipEventDestroy(p->order);
-    if (p->dblk)
-        (void)hipFree(p->dblk);
-    if (p->hblk)
-        (void)hipHostFree(p->hblk);
-    if (p->dbad_full)
-        (void)hipFree(p->dbad_full);
-    if (p->dspan_commit)
-        (void)hipFree(p->dspan_commit);
-    if (p->dpiece)
-        (void)hipFree(p->dpiece);
-    if (p->dpart)
-        (void)hipFree(p->dpart);
+    p->dblk.release();
+    p->hblk.release();
+    p->dbad_full.release();
+    p->dspan.release();
+    p->dpiece.release();
+    p->dpart.release();
     delete p;
 }
 
@@ -156,30 +151,31 @@ extern "C" int zscrc_cpass_create(zscrc_cpass **out, const zscrc_cpass_spec *spe
     std::vector<uint32_t> init(spec->nspans);
     for (size_t k = 0; k < spec->nspans; ++k)
         init[k] = zs_gf2_mul(0xFFFFFFFFu, zs_gf2_xpow8n(p->span_len[k]));
-    hipError_t e = hipMalloc(&p->dblk, 2 * BLK);
+    hipError_t e = zs::reserve_hip(p->dblk, 2 * BLK);
     if (e == hipSuccess)
-        e = hipMemset(p->dblk, 0, 2 * BLK); /* both blocks' counters start at 0 */
+        e = hipMemset(p->dblk.as<void>(), 0, 2 * BLK); /* both blocks' counters start at 0 */
     if (e == hipSuccess)
-        e = hipHostMalloc(reinterpret_cast<void **>(&p->hblk), NSLOT * BLK, hipHostMallocDefault);
+        e = zs::reserve_hip(p->hblk, NSLOT * BLK);
     for (int k = 0; k < NSLOT && e == hipSuccess; ++k)
         e = hipEventCreateWithFlags(&p->done[k], hipEventDisableTiming);
     if (e == hipSuccess)
         e = hipEventCreateWithFlags(&p->order, hipEventDisableTiming);
     if (e == hipSuccess)
-        e = hipMalloc(&p->dbad_full, 8 * p->cap);
+        e = zs::reserve_hip(p->dbad_full, 8 * p->cap);
     if (e == hipSuccess)
-        e = hipMalloc(&p->dspan_commit, (8 + 4) * zs::CPASS_SPANS);
+        e = zs::reserve_hip(p->dspan, (8 + 4) * zs::CPASS_SPANS);
     /* segment registers of the multi-span launches: any segment size is at
      * least 1 KiB (SEG_MIN), so this bounds every launch shape the tuning
      * can pick */
     for (size_t k = 0; k < spec->nspans; ++k)
         p->part_words += (p->span_len[k] + 1023) / 1024;
     if (e == hipSuccess && p->part_words)
-        e = hipMalloc(&p->dpart, 4 * p->part_words);
+        e = zs::reserve_hip(p->dpart, 4 * p->part_words);
     if (e != hipSuccess) {
         cpass_free(p);
         return ZSCRC_ENOMEM;
     }
+    p->dspan_commit = p->dspan.as<int64_t>();
     p->dspan_init = reinterpret_cast<uint32_t *>(p->dspan_commit + zs::CPASS_SPANS);
     if (spec->nspans &&
         (hipMemcpy(p->dspan_commit, p->span_commit.data(), 8 * spec->nspans, hipMemcpyHostToDevice) != hipSuccess ||
@@ -292,13 +288,13 @@ extern "C" int zscrc_cpass_set_row(zscrc_cpass *p, const zscrc_cpass_row_spec *r
         meta[3 * k + 1] = rs->piece_code[k];
         meta[3 * k + 2] = (int64_t)p->span_len[k];
     }
-    if (!p->dpiece && hipMalloc(&p->dpiece, 3 * 8 * zs::CPASS_SPANS) != hipSuccess)
+    if (p->dpiece.reserve(3 * 8 * zs::CPASS_SPANS))
         return ZSCRC_ENOMEM;
-    if (hipMemcpy(p->dpiece, meta.data(), 8 * meta.size(), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(p->dpiece.as<void>(), meta.data(), 8 * meta.size(), hipMemcpyHostToDevice) != hipSuccess)
         return ZSCRC_EHIP;
     zs::CPassRowArgs &a = p->row;
     memset(&a, 0, sizeof a);
-    a.blk = p->dblk; /* set per pass: the block it used */
+    a.blk = p->dblk.as<uint8_t>(); /* set per pass: the block it used */
     a.off_raw = OFF_RAW;
     a.off_st = OFF_ST;
     a.off_flags = OFF_FLAGS;
@@ -307,7 +303,7 @@ extern "C" int zscrc_cpass_set_row(zscrc_cpass *p, const zscrc_cpass_row_spec *r
     a.commits = p->spec.n;
     a.file = p->spec.d_file;
     a.rec = rs->d_rec;
-    a.piece = p->dpiece;
+    a.piece = p->dpiece.as<int64_t>();
     a.nspans = (uint32_t)p->spec.nspans;
     a.listed = rs->listed;
     a.pmax = rs->pmax;
@@ -354,7 +350,7 @@ int cpass_submit(zscrc_cpass *p, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1, 
      * sorting.  The caller's end event doubles as the slot's completion;
      * otherwise the slot's own */
     p->wait[slot] = ev1 ? ev1 : p->done[slot];
-    int rc = cpass_enqueue(p, s, ev0, &blk, p->hblk + slot * BLK, nullptr, p->wait[slot]);
+    int rc = cpass_enqueue(p, s, ev0, &blk, p->hblk.as<uint8_t>() + slot * BLK, nullptr, p->wait[slot]);
     if (!rc)
         p->pending[slot] = true;
     return rc;
@@ -400,13 +396,14 @@ int cpass_enqueue(zscrc_cpass *p, hipStream_t s, hipEvent_t ev0, uint8_t **blk, 
 int cpass_enqueue_on(zscrc_cpass *p, hipStream_t s, uint8_t **blk, uint8_t *host, int64_t *d_row, hipEvent_t done)
 {
     const zscrc_cpass_spec &sp = p->spec;
-    uint8_t *b = p->dblk + p->blk_next * BLK, *other = p->dblk + (p->blk_next ^ 1) * BLK;
+    uint8_t *const dblk = p->dblk.as<uint8_t>();
+    uint8_t *b = dblk + p->blk_next * BLK, *other = dblk + (p->blk_next ^ 1) * BLK;
     p->blk_next ^= 1;
     *blk = b;
     uint64_t *d_nbad = reinterpret_cast<uint64_t *>(b);
     uint32_t *d_raw = reinterpret_cast<uint32_t *>(b + OFF_RAW);
     int rc = zscrc_internal_verdict_prezeroed(sp.d_image, sp.image_size, sp.d_off, sp.d_len, sp.n, sp.max_len,
-                                              d_nbad, p->dbad_full, p->cap, s);
+                                              d_nbad, p->dbad_full.as<uint64_t>(), p->cap, s);
     /* raw spans: up to 8 of >= 16 KiB per launch pair, else one by one.
      * When they all make one multi-span launch (config 5: two records
      * regions, two pointer sections) and no row is built, its folds run in
@@ -428,7 +425,8 @@ int cpass_enqueue_on(zscrc_cpass *p, hipStream_t s, uint8_t **blk, uint8_t *host
         }
         if (k >= 2) {
             zs::SpanFolds *df = defer && k == sp.nspans ? &folds : nullptr;
-            rc = zscrc_internal_spans_private(bufs, lens, d_raw + i, k, ZSCRC_RAW, p->dpart, p->part_words, s, df);
+            rc = zscrc_internal_spans_private(bufs, lens, d_raw + i, k, ZSCRC_RAW, p->dpart.as<uint32_t>(),
+                                              p->part_words, s, df);
             if (rc == ZSCRC_EINVAL) /* a tuning without the one-launch shape: the shared path */
                 rc = zscrc_device_spans(bufs, lens, nullptr, d_raw + i, k, ZSCRC_RAW, s);
             else if (!rc && df)
@@ -448,7 +446,7 @@ int cpass_enqueue_on(zscrc_cpass *p, hipStream_t s, uint8_t **blk, uint8_t *host
         a.len = sp.d_len;
         a.file = sp.d_file;
         a.nbad = reinterpret_cast<const unsigned long long *>(d_nbad);
-        a.bad = p->dbad_full;
+        a.bad = p->dbad_full.as<uint64_t>();
         a.cap = p->cap;
         uint8_t *o = host ? host : b; /* where the listed verdict goes */
         a.flags = reinterpret_cast<uint32_t *>(o + OFF_FLAGS);
@@ -488,7 +486,7 @@ int cpass_collect(zscrc_cpass *p, int slot, zscrc_cpass_result *res)
     if (hipEventSynchronize(p->wait[slot]) != hipSuccess)
         return ZSCRC_EHIP;
     const zscrc_cpass_spec &sp = p->spec;
-    const uint8_t *blk = p->hblk + slot * BLK;
+    const uint8_t *blk = p->hblk.as<uint8_t>() + slot * BLK;
     const uint64_t nbad = reinterpret_cast<const uint64_t *>(blk)[0];
     /* the device's stale count over every classified entry (the post
      * kernel's last workgroup), not a recount of the listed flags: the same

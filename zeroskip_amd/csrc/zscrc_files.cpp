@@ -66,6 +66,7 @@
 #include <vector>
 
 #include "../../include/zscrc.h"
+#include "zscrc_buf_hip.h"
 
 namespace {
 
@@ -138,20 +139,19 @@ int device_list(std::vector<int> &out)
 struct Cache {
     std::mutex mu;
     int dev = -1;
-    uint64_t slot_bytes = 0;
-    uint8_t *slot[NSLOT] = {};
-    uint8_t *dimg = nullptr;
-    uint64_t dimg_bytes = 0;
+    zs::PinBuf slot[NSLOT];
+    zs::DevBuf dimg;
     /* commit descriptors: pinned SoA arrays (written by the walkers), their
      * device copy and the device results */
-    uint64_t dcap = 0;
-    uint64_t *h_off = nullptr, *h_len = nullptr;
-    uint32_t *h_st = nullptr;
-    uint8_t *ddesc = nullptr;
-    uint64_t ddesc_bytes = 0;
-    uint64_t *h_bad = nullptr; /* pinned: the verdict's count + listed indices */
-    uint8_t *dq = nullptr;     /* device: the stale-commit re-verification batch */
-    uint64_t dq_bytes = 0;
+    zs::PinBuf desc[3]; /* h_off, h_len, h_st: grown together (ensure_desc) */
+    uint64_t *h_off() const { return desc[0].as<uint64_t>(); }
+    uint64_t *h_len() const { return desc[1].as<uint64_t>(); }
+    uint32_t *h_st() const { return desc[2].as<uint32_t>(); }
+    /* commits the arrays hold: the last one allocated has its bytes only when all three have */
+    uint64_t dcap() const { return desc[2].bytes() / 4; }
+    zs::DevBuf ddesc;
+    zs::PinBuf h_bad; /* the verdict's count + listed indices */
+    zs::DevBuf dq;    /* the stale-commit re-verification batch */
     /* copy and compute streams and their events, kept across calls (creating
      * and destroying them per group cost milliseconds per call) */
     hipStream_t cs = nullptr, ks = nullptr;
@@ -205,97 +205,31 @@ void cache_free(Cache &c)
 {
     if (c.dev >= 0)
         (void)hipSetDevice(c.dev);
-    for (int k = 0; k < NSLOT; ++k)
-        if (c.slot[k])
-            (void)hipHostFree(c.slot[k]);
-    if (c.h_off)
-        (void)hipHostFree(c.h_off);
-    if (c.h_len)
-        (void)hipHostFree(c.h_len);
-    if (c.h_st)
-        (void)hipHostFree(c.h_st);
-    if (c.dimg)
-        (void)hipFree(c.dimg);
-    if (c.ddesc)
-        (void)hipFree(c.ddesc);
-    if (c.h_bad)
-        (void)hipHostFree(c.h_bad);
-    if (c.dq)
-        (void)hipFree(c.dq);
-    sync_free(c);
-    const int dev = c.dev;
-    c.dev = dev; /* keep the binding; everything else reset */
-    c.slot_bytes = 0;
-    for (auto &s : c.slot)
-        s = nullptr;
-    c.dimg = nullptr;
-    c.dimg_bytes = 0;
-    c.dcap = 0;
-    c.h_off = c.h_len = nullptr;
-    c.h_st = nullptr;
-    c.ddesc = nullptr;
-    c.ddesc_bytes = 0;
-    c.h_bad = nullptr;
-    c.dq = nullptr;
-    c.dq_bytes = 0;
+    zs::release_all(c.slot);
+    zs::release_all(c.desc);
+    c.dimg.release();
+    c.ddesc.release();
+    c.h_bad.release();
+    c.dq.release();
+    sync_free(c); /* c.dev, the binding, is kept */
 }
 
-int grow_dev(uint8_t **p, uint64_t *have, uint64_t need)
+/* A device buffer grown to `need` bytes and an eighth more. */
+int grow_dev(zs::DevBuf &b, uint64_t need)
 {
-    if (*have >= need)
-        return ZSCRC_OK;
-    if (*p)
-        (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    need += need / 8;
-    if (hipMalloc(reinterpret_cast<void **>(p), need) != hipSuccess)
-        return ZSCRC_ENOMEM;
-    *have = need;
-    return ZSCRC_OK;
+    return b.reserve(need, need / 8);
 }
 
-int ensure_slots(Cache &c, uint64_t slot_bytes)
-{
-    if (c.slot_bytes >= slot_bytes)
-        return ZSCRC_OK;
-    for (int k = 0; k < NSLOT; ++k) {
-        if (c.slot[k])
-            (void)hipHostFree(c.slot[k]);
-        c.slot[k] = nullptr;
-    }
-    c.slot_bytes = 0;
-    for (int k = 0; k < NSLOT; ++k)
-        if (hipHostMalloc(reinterpret_cast<void **>(&c.slot[k]), slot_bytes, hipHostMallocDefault) != hipSuccess)
-            return ZSCRC_ENOMEM;
-    c.slot_bytes = slot_bytes;
-    return ZSCRC_OK;
-}
-
-/* Pinned descriptor arrays for at least `count` commits (contents dropped). */
+/* Pinned descriptor arrays for at least `count` commits (contents dropped);
+ * when they grow, the verdict's block if there is none yet. */
 int ensure_desc(Cache &c, uint64_t count)
 {
-    if (c.dcap >= count)
+    static const size_t width[3] = {8, 8, 4};
+    if (c.dcap() >= count)
         return ZSCRC_OK;
-    if (c.h_off)
-        (void)hipHostFree(c.h_off);
-    if (c.h_len)
-        (void)hipHostFree(c.h_len);
-    if (c.h_st)
-        (void)hipHostFree(c.h_st);
-    c.h_off = c.h_len = nullptr;
-    c.h_st = nullptr;
-    c.dcap = 0;
-    count += count / 4 + 1024;
-    if (hipHostMalloc(reinterpret_cast<void **>(&c.h_off), 8 * count, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&c.h_len), 8 * count, hipHostMallocDefault) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&c.h_st), 4 * count, hipHostMallocDefault) != hipSuccess)
-        return ZSCRC_ENOMEM;
-    c.dcap = count;
-    if (!c.h_bad &&
-        hipHostMalloc(reinterpret_cast<void **>(&c.h_bad), 8 * (VCAP + 1), hipHostMallocDefault) != hipSuccess)
-        return ZSCRC_ENOMEM;
-    return ZSCRC_OK;
+    if (const int rc = zs::reserve_all(c.desc, count, count / 4 + 1024, width))
+        return rc;
+    return c.h_bad.reserve(8 * (VCAP + 1));
 }
 
 /* ------------------------------------------------------------ the plan */
@@ -446,13 +380,14 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
         est += (x->what == EXT_FILE ? (x->hi - x->lo) / 256 : 0) + 4;
     }
     const uint64_t slot = C.slot_bytes;
-    int rc = C.direct ? ZSCRC_OK : ensure_slots(cache, slot);
+    int rc = C.direct ? ZSCRC_OK : zs::reserve_all(cache.slot, slot);
     if (!rc)
-        rc = grow_dev(&cache.dimg, &cache.dimg_bytes, std::max<uint64_t>(total, ALIGN));
-    if (!rc && cache.dcap == 0)
+        rc = grow_dev(cache.dimg, std::max<uint64_t>(total, ALIGN));
+    if (!rc && cache.dcap() == 0)
         rc = ensure_desc(cache, est); /* later calls keep what the largest needed */
     if (rc)
         return rc;
+    uint8_t *const dimg = cache.dimg.as<uint8_t>();
     const uint64_t npiece = (total + slot - 1) / slot;
 
     struct Task {
@@ -494,7 +429,7 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
     std::atomic<size_t> walks_left{ng};
     std::atomic<uint64_t> dpos{0};          /* descriptor bump index */
     std::atomic<uint64_t> max_len{0}, min_len{~0ull};
-    const uint64_t dcap = cache.dcap;
+    const uint64_t dcap = cache.dcap();
 
     auto worker = [&]() {
         for (;;) {
@@ -516,7 +451,7 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
                  * results go back by position) */
                 x.pos = dpos.fetch_add(x.ncommit, std::memory_order_relaxed);
                 if (x.pos + x.ncommit <= dcap)
-                    place(x, cache.h_off, cache.h_len);
+                    place(x, cache.h_off(), cache.h_len());
                 walks_left.fetch_sub(1, std::memory_order_acq_rel);
                 continue;
             }
@@ -529,7 +464,7 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
             const uint64_t base = p * slot;
             const uint64_t lo = base + tk.b * SUB;
             const uint64_t hi = std::min(std::min(total, base + slot), lo + SUB);
-            uint8_t *dst = cache.slot[p % NSLOT] - base;
+            uint8_t *dst = cache.slot[p % NSLOT].as<uint8_t>() - base;
             /* the extents overlapping [lo, hi) (each padded to ALIGN with zeros) */
             size_t f = std::upper_bound(G.begin(), G.end(), lo,
                                         [](uint64_t v, const Ext *q) { return v < q->dev_off; }) -
@@ -573,31 +508,31 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
         ncommit = dpos.load();
         if (ncommit > dcap) {
             /* nothing reads the old arrays yet: regrow and place every extent */
-            std::vector<uint64_t> oo(cache.h_off, cache.h_off + std::min(ncommit, dcap));
-            std::vector<uint64_t> ol(cache.h_len, cache.h_len + std::min(ncommit, dcap));
+            std::vector<uint64_t> oo(cache.h_off(), cache.h_off() + std::min(ncommit, dcap));
+            std::vector<uint64_t> ol(cache.h_len(), cache.h_len() + std::min(ncommit, dcap));
             int r = ensure_desc(cache, ncommit);
             if (r)
                 return r;
             for (Ext *x : G) {
                 if (x->placed) {
-                    memcpy(cache.h_off + x->pos, oo.data() + x->pos, 8 * x->ncommit);
-                    memcpy(cache.h_len + x->pos, ol.data() + x->pos, 8 * x->ncommit);
+                    memcpy(cache.h_off() + x->pos, oo.data() + x->pos, 8 * x->ncommit);
+                    memcpy(cache.h_len() + x->pos, ol.data() + x->pos, 8 * x->ncommit);
                 } else {
-                    place(*x, cache.h_off, cache.h_len);
+                    place(*x, cache.h_off(), cache.h_len());
                 }
             }
         }
         /* + the verdict (count + VCAP indices) after the raw registers */
-        int r = grow_dev(&cache.ddesc, &cache.ddesc_bytes, 24 * ncommit + 4 * pieces.size() + 8 * (VCAP + 2) + 1024);
+        int r = grow_dev(cache.ddesc, 24 * ncommit + 4 * pieces.size() + 8 * (VCAP + 2) + 1024);
         if (r)
             return r;
-        doff = reinterpret_cast<uint64_t *>(cache.ddesc);
+        doff = cache.ddesc.as<uint64_t>();
         dlen = doff + ncommit;
         dcrc = reinterpret_cast<uint32_t *>(dlen + ncommit);
         dst = dcrc + ncommit;
         draw = dst + ncommit;
-        if (ncommit && (hipMemcpyAsync(doff, cache.h_off, 8 * ncommit, hipMemcpyHostToDevice, cs) != hipSuccess ||
-                        hipMemcpyAsync(dlen, cache.h_len, 8 * ncommit, hipMemcpyHostToDevice, cs) != hipSuccess))
+        if (ncommit && (hipMemcpyAsync(doff, cache.h_off(), 8 * ncommit, hipMemcpyHostToDevice, cs) != hipSuccess ||
+                        hipMemcpyAsync(dlen, cache.h_len(), 8 * ncommit, hipMemcpyHostToDevice, cs) != hipSuccess))
             return ZSCRC_EHIP;
         desc_sent = true;
         return ZSCRC_OK;
@@ -616,7 +551,7 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
                 bytes += G[g]->hi - G[g]->lo;
                 ++g;
             }
-            if (bytes && hipMemcpyAsync(cache.dimg + G[f]->dev_off, src, bytes, hipMemcpyHostToDevice, cs) !=
+            if (bytes && hipMemcpyAsync(dimg + G[f]->dev_off, src, bytes, hipMemcpyHostToDevice, cs) !=
                              hipSuccess)
                 rc = ZSCRC_EHIP;
             if (!rc && !desc_sent && walks_left.load(std::memory_order_acquire) == 0)
@@ -629,7 +564,7 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
             std::this_thread::yield();
         const int k = (int)(p % NSLOT);
         const uint64_t lo = p * slot, hi = std::min(total, lo + slot);
-        if (hipMemcpyAsync(cache.dimg + lo, cache.slot[k], hi - lo, hipMemcpyHostToDevice, cs) != hipSuccess ||
+        if (hipMemcpyAsync(dimg + lo, cache.slot[k].as<void>(), hi - lo, hipMemcpyHostToDevice, cs) != hipSuccess ||
             hipEventRecord(slot_ev[k], cs) != hipSuccess) {
             rc = ZSCRC_EHIP;
             break;
@@ -665,10 +600,11 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
     const uint64_t vcap = std::min<uint64_t>(VCAP, ncommit);
     if (!rc && ncommit) {
         /* the walks' length range: classes outside it get no launch */
-        rc = zscrc_device_verify_commits_verdict_range(cache.dimg, total, doff, dlen, nullptr, ncommit,
+        rc = zscrc_device_verify_commits_verdict_range(dimg, total, doff, dlen, nullptr, ncommit,
                                                        std::min(min_len.load(), max_len.load()), max_len.load(),
                                                        d_nbad, d_nbad + 1, vcap, ks);
-        if (!rc && hipMemcpyAsync(cache.h_bad, d_nbad, 8 * (vcap + 1), hipMemcpyDeviceToHost, ks) != hipSuccess)
+        if (!rc && hipMemcpyAsync(cache.h_bad.as<void>(), d_nbad, 8 * (vcap + 1), hipMemcpyDeviceToHost, ks) !=
+                       hipSuccess)
             rc = ZSCRC_EHIP;
     }
     std::vector<uint32_t> raw(pieces.size());
@@ -680,7 +616,7 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
         while (!rc && i < pieces.size()) {
             size_t k = 0;
             while (k < 8 && i + k < pieces.size() && pieces[i + k]->hi - pieces[i + k]->lo >= (16u << 10)) {
-                bufs[k] = cache.dimg + pieces[i + k]->dev_off;
+                bufs[k] = dimg + pieces[i + k]->dev_off;
                 lens[k] = pieces[i + k]->hi - pieces[i + k]->lo;
                 ++k;
             }
@@ -688,7 +624,7 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
                 rc = zscrc_device_spans(bufs, lens, nullptr, draw + i, k, ZSCRC_RAW, ks);
                 i += k;
             } else {
-                rc = zscrc_device_span(cache.dimg + pieces[i]->dev_off, pieces[i]->hi - pieces[i]->lo, 0, draw + i,
+                rc = zscrc_device_span(dimg + pieces[i]->dev_off, pieces[i]->hi - pieces[i]->lo, 0, draw + i,
                                        nullptr, ZSCRC_RAW, ks);
                 ++i;
             }
@@ -708,18 +644,19 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
     /* mismatches (status != 1), by descriptor position -> extent */
     std::vector<uint64_t> badpos;
     if (!rc && ncommit) {
-        const uint64_t nbad = cache.h_bad[0];
+        const uint64_t *h_bad = cache.h_bad.as<uint64_t>();
+        const uint64_t nbad = h_bad[0];
         if (nbad <= vcap) {
-            badpos.assign(cache.h_bad + 1, cache.h_bad + 1 + nbad);
+            badpos.assign(h_bad + 1, h_bad + 1 + nbad);
             std::sort(badpos.begin(), badpos.end());
         } else {
             /* more than the list holds: every commit's status */
-            rc = zscrc_device_verify_commits_bounded(cache.dimg, total, doff, dlen, nullptr, ncommit, max_len.load(),
+            rc = zscrc_device_verify_commits_bounded(dimg, total, doff, dlen, nullptr, ncommit, max_len.load(),
                                                      dcrc, dst, ks);
-            if (!rc && (hipMemcpyAsync(cache.h_st, dst, 4 * ncommit, hipMemcpyDeviceToHost, ks) != hipSuccess ||
+            if (!rc && (hipMemcpyAsync(cache.h_st(), dst, 4 * ncommit, hipMemcpyDeviceToHost, ks) != hipSuccess ||
                         hipStreamSynchronize(ks) != hipSuccess))
                 rc = ZSCRC_EHIP;
-            const uint32_t *st = cache.h_st;
+            const uint32_t *st = cache.h_st();
             for (uint64_t i = 0; !rc && i < ncommit; ++i)
                 if (st[i] != 1)
                     badpos.push_back(i);
@@ -739,7 +676,7 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
     /* stale zero-length commits: chained from the previous span's CRC */
     std::vector<uint64_t> cand;
     for (uint64_t i : badpos) {
-        if (cache.h_len[i] == 0 && i > ext_of(i).pos)
+        if (cache.h_len()[i] == 0 && i > ext_of(i).pos)
             cand.push_back(i);
     }
     std::vector<uint32_t> st2(cand.size());
@@ -749,23 +686,23 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
         uint64_t prev_max = 0;
         for (size_t c = 0; c < m; ++c) {
             const uint64_t i = cand[c];
-            prev_max = std::max(prev_max, cache.h_len[i - 1]);
-            q[c] = cache.h_off[i - 1];
-            q[m + c] = cache.h_len[i - 1];
-            q[2 * m + c] = cache.h_off[i];
-            q[3 * m + c] = cache.h_len[i];
+            prev_max = std::max(prev_max, cache.h_len()[i - 1]);
+            q[c] = cache.h_off()[i - 1];
+            q[m + c] = cache.h_len()[i - 1];
+            q[2 * m + c] = cache.h_off()[i];
+            q[3 * m + c] = cache.h_len()[i];
         }
-        /* a cached device buffer: a hipMalloc / hipFree per call cost a
+        /* a cached device buffer: an allocation and a free per call cost a
          * device-wide synchronisation each */
-        rc = grow_dev(&cache.dq, &cache.dq_bytes, 4 * m * 8 + 3 * m * 4);
-        uint64_t *dq = rc ? nullptr : reinterpret_cast<uint64_t *>(cache.dq);
+        rc = grow_dev(cache.dq, 4 * m * 8 + 3 * m * 4);
+        uint64_t *dq = rc ? nullptr : cache.dq.as<uint64_t>();
         uint32_t *dprev = dq ? reinterpret_cast<uint32_t *>(dq + 4 * m) : nullptr;
         if (!rc && hipMemcpyAsync(dq, q.data(), 4 * m * 8, hipMemcpyHostToDevice, ks) != hipSuccess)
             rc = ZSCRC_EHIP;
         if (!rc)
-            rc = zscrc_device_batch_bounded(cache.dimg, dq, dq + m, nullptr, dprev, m, 0, prev_max, ks);
+            rc = zscrc_device_batch_bounded(dimg, dq, dq + m, nullptr, dprev, m, 0, prev_max, ks);
         if (!rc)
-            rc = zscrc_device_verify_commits_bounded(cache.dimg, total, dq + 2 * m, dq + 3 * m, dprev, m, 0,
+            rc = zscrc_device_verify_commits_bounded(dimg, total, dq + 2 * m, dq + 3 * m, dprev, m, 0,
                                                      dprev + m, dprev + 2 * m, ks);
         if (!rc && (hipMemcpyAsync(st2.data(), dprev + 2 * m, m * 4, hipMemcpyDeviceToHost, ks) != hipSuccess ||
                     hipStreamSynchronize(ks) != hipSuccess))
@@ -784,7 +721,7 @@ int run_group(Call &C, Cache &cache, std::vector<Ext *> &G, int threads)
             }
             C.acc.bad++;
             const Ext &x = ext_of(i);
-            C.acc.first(x.file, cache.h_off[i] - x.dev_off + x.lo + cache.h_len[i], ZSCRC_FILES_BAD_COMMIT);
+            C.acc.first(x.file, cache.h_off()[i] - x.dev_off + x.lo + cache.h_len()[i], ZSCRC_FILES_BAD_COMMIT);
         }
     }
     /* nothing of this group left queued on the cached streams (error paths
@@ -900,7 +837,7 @@ extern "C" int zscrc_zs_verify_files(const void *const *images, const uint64_t *
         const uint64_t share = (uint64_t)std::count(devs.begin(), devs.end(), devs[s]);
         uint64_t held = 0;
         if (g_cache[s].dev == devs[s])
-            held = g_cache[s].dimg_bytes;
+            held = g_cache[s].dimg.bytes();
         group = std::min<uint64_t>(group, (fr / share + held) / 2);
     }
     (void)hipSetDevice(cur);
@@ -1020,11 +957,8 @@ extern "C" int zscrc_zs_verify_files(const void *const *images, const uint64_t *
         }
         flush();
         /* the buffer never holds more than one group; beyond that, free it */
-        if (cache.dimg_bytes > group + group / 8) {
-            (void)hipFree(cache.dimg);
-            cache.dimg = nullptr;
-            cache.dimg_bytes = 0;
-        }
+        if (cache.dimg.bytes() > group + group / 8)
+            cache.dimg.release();
     };
     if (S == 1) {
         run_slot(0);

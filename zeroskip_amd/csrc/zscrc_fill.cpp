@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "../../include/zscrc.h"
+#include "zscrc_buf_hip.h"
 
 extern "C" int zs_launch_widen_desc(const uint32_t *pairs, uint64_t *off, uint64_t *len, uint64_t n,
                                     hipStream_t stream);
@@ -91,18 +92,16 @@ inline uint64_t rec_len(const uint8_t *img, uint64_t size, uint64_t at)
  * device), the device image ring. */
 struct Cache {
     std::mutex mu;
-    uint64_t slot_bytes = 0;
-    uint8_t *slot[NSLOT] = {};
-    uint64_t ring_bytes = 0;
-    uint8_t *dring[RING] = {};
-    uint64_t ring_commits = 0;
-    uint32_t *dpairs[RING] = {};
+    zs::PinBuf slot[NSLOT];
+    zs::DevBuf dring[RING];
+    /* per commit of a chunk: pairs (8 B), then off (8), len (8), crc (4) */
+    zs::DevBuf dpairs[RING];
     uint64_t *doff[RING] = {};
     uint64_t *dlen[RING] = {};
     uint32_t *dcrc[RING] = {};
-    uint64_t host_commits = 0;
-    uint32_t *hpairs = nullptr; /* 2 x n */
-    uint32_t *hcrc = nullptr;   /* n */
+    zs::PinBuf host[2]; /* hpairs, hcrc: grown together */
+    uint32_t *hpairs() const { return host[0].as<uint32_t>(); } /* 2 x n */
+    uint32_t *hcrc() const { return host[1].as<uint32_t>(); }   /* n */
     /* copy / kernel / copy-back streams and per-chunk events, kept across
      * calls: creating and destroying them per call cost milliseconds */
     hipStream_t cs = nullptr, ks = nullptr, os = nullptr;
@@ -142,65 +141,22 @@ Cache g_cache[MAX_DEV];
 
 int ensure(Cache &c, bool staged, uint64_t chunk_bytes, uint64_t chunk_commits, uint64_t n)
 {
-    if (staged && c.slot_bytes < chunk_bytes) {
-        for (auto &s : c.slot) {
-            if (s)
-                (void)hipHostFree(s);
-            s = nullptr;
-        }
-        c.slot_bytes = 0;
-        for (auto &s : c.slot)
-            if (hipHostMalloc(reinterpret_cast<void **>(&s), chunk_bytes, hipHostMallocDefault) != hipSuccess)
-                return ZSCRC_ENOMEM;
-        c.slot_bytes = chunk_bytes;
+    int rc = staged ? zs::reserve_all(c.slot, chunk_bytes) : ZSCRC_OK;
+    if (!rc) /* 256: the image's alignment within 256 B is kept on the device */
+        rc = zs::reserve_all(c.dring, chunk_bytes + 256);
+    /* 28 m + 64 bytes for m = chunk_commits + chunk_commits / 4 + 64 commits */
+    if (!rc)
+        rc = zs::reserve_all(c.dpairs, 28 * chunk_commits + 64, 28 * (chunk_commits / 4 + 64));
+    if (rc)
+        return rc;
+    const uint64_t m = (c.dpairs[0].bytes() - 64) / 28;
+    for (int r = 0; r < RING; ++r) {
+        c.doff[r] = reinterpret_cast<uint64_t *>(c.dpairs[r].as<uint8_t>() + 8 * m);
+        c.dlen[r] = c.doff[r] + m;
+        c.dcrc[r] = reinterpret_cast<uint32_t *>(c.dlen[r] + m);
     }
-    if (c.ring_bytes < chunk_bytes + 256) {
-        for (auto &b : c.dring) {
-            if (b)
-                (void)hipFree(b);
-            b = nullptr;
-        }
-        c.ring_bytes = 0;
-        for (auto &b : c.dring)
-            if (hipMalloc(&b, chunk_bytes + 256) != hipSuccess)
-                return ZSCRC_ENOMEM;
-        c.ring_bytes = chunk_bytes + 256;
-    }
-    if (c.ring_commits < chunk_commits) {
-        for (int r = 0; r < RING; ++r) {
-            if (c.dpairs[r])
-                (void)hipFree(c.dpairs[r]);
-            c.dpairs[r] = nullptr;
-        }
-        c.ring_commits = 0;
-        const uint64_t m = chunk_commits + chunk_commits / 4 + 64;
-        for (int r = 0; r < RING; ++r) {
-            /* pairs (8 B) + off (8) + len (8) + crc (4) per commit */
-            uint8_t *p = nullptr;
-            if (hipMalloc(&p, 28 * m + 64) != hipSuccess)
-                return ZSCRC_ENOMEM;
-            c.dpairs[r] = reinterpret_cast<uint32_t *>(p);
-            c.doff[r] = reinterpret_cast<uint64_t *>(p + 8 * m);
-            c.dlen[r] = c.doff[r] + m;
-            c.dcrc[r] = reinterpret_cast<uint32_t *>(c.dlen[r] + m);
-        }
-        c.ring_commits = m;
-    }
-    if (c.host_commits < n) {
-        if (c.hpairs)
-            (void)hipHostFree(c.hpairs);
-        if (c.hcrc)
-            (void)hipHostFree(c.hcrc);
-        c.hpairs = nullptr;
-        c.hcrc = nullptr;
-        c.host_commits = 0;
-        const uint64_t m = n + n / 4 + 1024;
-        if (hipHostMalloc(reinterpret_cast<void **>(&c.hpairs), 8 * m, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void **>(&c.hcrc), 4 * m, hipHostMallocDefault) != hipSuccess)
-            return ZSCRC_ENOMEM;
-        c.host_commits = m;
-    }
-    return ZSCRC_OK;
+    static const size_t width[2] = {8, 4};
+    return zs::reserve_all(c.host, n, n / 4 + 1024, width);
 }
 
 struct Chunk {
@@ -366,7 +322,7 @@ extern "C" int zscrc_zs_fill_commits(void *image, uint64_t size, const uint64_t 
             }
             const Chunk &ch = chunks[tk.k];
             if (tk.kind == 0) {
-                uint32_t *p = c.hpairs + 2 * ch.i0;
+                uint32_t *p = c.hpairs() + 2 * ch.i0;
                 uint64_t prev = ch.i0 ? span_end(ch.i0 - 1) : 0;
                 bool ok = true;
                 for (uint64_t i = ch.i0; i < ch.i1; ++i) {
@@ -387,7 +343,7 @@ extern "C" int zscrc_zs_fill_commits(void *image, uint64_t size, const uint64_t 
                         return;
                     (void)hipEventSynchronize(h2d[k - NSLOT]);
                 }
-                memcpy(c.slot[k % NSLOT] + tk.a, img + ch.lo + tk.a, tk.b - tk.a);
+                memcpy(c.slot[k % NSLOT].as<uint8_t>() + tk.a, img + ch.lo + tk.a, tk.b - tk.a);
             } else {
                 if (!wait_issued((int64_t)tk.k))
                     return;
@@ -407,7 +363,7 @@ extern "C" int zscrc_zs_fill_commits(void *image, uint64_t size, const uint64_t 
                         ++none;
                         continue;
                     }
-                    const uint32_t v = __builtin_bswap32(c.hcrc[i]);
+                    const uint32_t v = __builtin_bswap32(c.hcrc()[i]);
                     memcpy(img + at + (rl == 8 ? 4 : 20), &v, 4);
                     ++done;
                 }
@@ -433,7 +389,7 @@ extern "C" int zscrc_zs_fill_commits(void *image, uint64_t size, const uint64_t 
         const int r = (int)(k % RING);
         const uint64_t m = ch.i1 - ch.i0;
         const uint64_t shift = ch.lo & 255; /* the image's alignment within 256 B, kept on the device */
-        uint8_t *dimg = c.dring[r] + shift;
+        uint8_t *dimg = c.dring[r].as<uint8_t>() + shift;
         /* ring buffer r is free once chunk k - RING's kernel and D2H are done */
         if (k >= (size_t)RING && (hipStreamWaitEvent(cs, kern[k - RING], 0) != hipSuccess ||
                                   hipStreamWaitEvent(cs, d2h[k - RING], 0) != hipSuccess))
@@ -442,26 +398,26 @@ extern "C" int zscrc_zs_fill_commits(void *image, uint64_t size, const uint64_t 
          * a staged one once its slot is filled (the slot copies are in ready) */
         if (staged)
             wait_ready(k);
-        const void *src = staged ? static_cast<const void *>(c.slot[k % NSLOT]) : img + ch.lo;
+        const void *src = staged ? c.slot[k % NSLOT].as<const void>() : img + ch.lo;
         if (!rc && hipMemcpyAsync(dimg, src, ch.hi - ch.lo, hipMemcpyHostToDevice, cs) != hipSuccess)
             rc = ZSCRC_EHIP;
         if (k == 0)
             rep->setup_s = now_s() - t0;
         if (!staged)
             wait_ready(k);
-        if (!rc && (hipMemcpyAsync(c.dpairs[r], c.hpairs + 2 * ch.i0, 8 * m, hipMemcpyHostToDevice, cs) !=
+        if (!rc && (hipMemcpyAsync(c.dpairs[r].as<void>(), c.hpairs() + 2 * ch.i0, 8 * m, hipMemcpyHostToDevice, cs) !=
                         hipSuccess ||
                     hipEventRecord(h2d[k], cs) != hipSuccess))
             rc = ZSCRC_EHIP;
         if (!rc && hipStreamWaitEvent(ks, h2d[k], 0) != hipSuccess)
             rc = ZSCRC_EHIP;
-        if (!rc && zs_launch_widen_desc(c.dpairs[r], c.doff[r], c.dlen[r], m, ks))
+        if (!rc && zs_launch_widen_desc(c.dpairs[r].as<uint32_t>(), c.doff[r], c.dlen[r], m, ks))
             rc = ZSCRC_EHIP;
         if (!rc)
             rc = zscrc_device_commit_crcs_bounded(dimg, ch.hi - ch.lo, c.doff[r], c.dlen[r], m, max_len, c.dcrc[r],
                                                   nullptr, ks);
         if (!rc && (hipEventRecord(kern[k], ks) != hipSuccess || hipStreamWaitEvent(os, kern[k], 0) != hipSuccess ||
-                    hipMemcpyAsync(c.hcrc + ch.i0, c.dcrc[r], 4 * m, hipMemcpyDeviceToHost, os) != hipSuccess ||
+                    hipMemcpyAsync(c.hcrc() + ch.i0, c.dcrc[r], 4 * m, hipMemcpyDeviceToHost, os) != hipSuccess ||
                     hipEventRecord(d2h[k], os) != hipSuccess))
             rc = ZSCRC_EHIP;
         if (!rc)
@@ -536,7 +492,7 @@ extern "C" void zs_fill_release_cache(void)
     for (int d = 0; d < MAX_DEV; ++d) {
         Cache &c = g_cache[d];
         std::lock_guard<std::mutex> lk(c.mu);
-        if (!c.cs && !c.slot_bytes && !c.ring_bytes && !c.ring_commits && !c.host_commits)
+        if (!c.cs && !c.slot[0].bytes() && !c.dring[0].bytes() && !c.dpairs[0].bytes() && !c.host[0].bytes())
             continue;
         (void)hipSetDevice(d);
         for (hipStream_t *st : {&c.cs, &c.ks, &c.os})
@@ -550,29 +506,14 @@ extern "C" void zs_fill_release_cache(void)
                 (void)hipEventDestroy(e);
             v->clear();
         }
-        for (auto &p : c.slot) {
-            if (p)
-                (void)hipHostFree(p);
-            p = nullptr;
-        }
-        for (auto &p : c.dring) {
-            if (p)
-                (void)hipFree(p);
-            p = nullptr;
-        }
+        zs::release_all(c.slot);
+        zs::release_all(c.dring);
+        zs::release_all(c.dpairs);
         for (int r = 0; r < RING; ++r) {
-            if (c.dpairs[r])
-                (void)hipFree(c.dpairs[r]);
-            c.dpairs[r] = nullptr;
             c.doff[r] = c.dlen[r] = nullptr;
             c.dcrc[r] = nullptr;
         }
-        if (c.hpairs)
-            (void)hipHostFree(c.hpairs);
-        if (c.hcrc)
-            (void)hipHostFree(c.hcrc);
-        c.hpairs = c.hcrc = nullptr;
-        c.slot_bytes = c.ring_bytes = c.ring_commits = c.host_commits = 0;
+        zs::release_all(c.host);
     }
     if (cur >= 0)
         (void)hipSetDevice(cur);

@@ -9,6 +9,7 @@
 #include <mutex>
 
 #include "../../include/zscrc.h"
+#include "zscrc_buf_hip.h"
 #include "zscrc_carve.h"
 
 /* Global operator-table block (uint32 words), built on the host per device. */
@@ -45,16 +46,14 @@ inline bool same_stream(hipStream_t a, hipStream_t b)
  * another stream than the last user's waits for that user's work. */
 struct Scratch {
     std::mutex mu;
-    void *p = nullptr;
-    size_t bytes = 0;
+    DevBuf buf;
     hipEvent_t last = nullptr;
     hipStream_t last_stream = nullptr;
     bool last_valid = false;
     /* zscrc_device_walk_multi, zscrc_device_merge: pinned staging of the image
      * or list descriptors on their way to the device, reused once its last
      * copy has run (staged) */
-    void *pin = nullptr;
-    size_t pin_bytes = 0;
+    PinBuf pin;
     hipEvent_t staged = nullptr;
     bool staged_valid = false;
 };
@@ -91,7 +90,7 @@ int with_scratch(void *own, size_t need, bool staging, hipStream_t s, F f)
     if (own)
         return f(own, sc);
     const int rc = scratch_acquire(*sc, need, s);
-    return rc ? rc : scratch_done(*sc, s, f(sc->p, sc));
+    return rc ? rc : scratch_done(*sc, s, f(sc->buf.as<void>(), sc));
 }
 
 struct RecDesc;

@@ -33,18 +33,11 @@ Scratch *device_scratch()
 
 int scratch_acquire(Scratch &sc, size_t need, hipStream_t s)
 {
-    if (sc.bytes < need) {
-        if (sc.p)
-            (void)hipFree(sc.p); /* waits for the device: no user is left */
-        sc.p = nullptr;
-        sc.bytes = 0;
+    if (sc.buf.bytes() < need) {
         sc.last_valid = false;
-        /* about the image's size: no slack on top */
-        if (hipMalloc(&sc.p, need) != hipSuccess) {
-            sc.p = nullptr;
-            return ZSCRC_ENOMEM;
-        }
-        sc.bytes = need;
+        /* the free waits for the device: no user is left; about the image's size: no slack on top */
+        if (const int rc = sc.buf.reserve(need))
+            return rc;
     }
     /* a wait on the stream's own event is harmless: "not certainly the same stream" waits */
     if (sc.last_valid && !zs::same_stream(sc.last_stream, s) && hipStreamWaitEvent(s, sc.last, 0) != hipSuccess)
@@ -69,23 +62,12 @@ int stage_begin(Scratch &sc, size_t bytes)
     if (sc.staged_valid && hipEventSynchronize(sc.staged) != hipSuccess)
         return ZSCRC_EHIP;
     sc.staged_valid = false;
-    if (sc.pin_bytes < bytes) {
-        if (sc.pin)
-            (void)hipHostFree(sc.pin);
-        sc.pin = nullptr;
-        sc.pin_bytes = 0;
-        if (hipHostMalloc(&sc.pin, bytes, hipHostMallocDefault) != hipSuccess) {
-            sc.pin = nullptr;
-            return ZSCRC_ENOMEM;
-        }
-        sc.pin_bytes = bytes;
-    }
-    return ZSCRC_OK;
+    return sc.pin.reserve(bytes);
 }
 
 int stage_copy(Scratch &sc, void *d_dst, size_t bytes, hipStream_t s)
 {
-    if (hipMemcpyAsync(d_dst, sc.pin, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+    if (hipMemcpyAsync(d_dst, sc.pin.as<void>(), bytes, hipMemcpyHostToDevice, s) != hipSuccess)
         return ZSCRC_EHIP;
     if (!sc.staged && hipEventCreateWithFlags(&sc.staged, hipEventDisableTiming) != hipSuccess)
         sc.staged = nullptr;
@@ -123,7 +105,7 @@ int stage_lists(zs::Scratch &sc, const zscrc_merge_list *lists, size_t k, uint32
     const int rc = zs::stage_begin(sc, bytes);
     if (rc)
         return rc;
-    ListD *h = static_cast<ListD *>(sc.pin);
+    ListD *h = sc.pin.as<ListD>();
     uint64_t first = 0;
     for (size_t l = 0; l < k; ++l) {
         if (!lists[l].n)
@@ -156,25 +138,19 @@ extern "C" void zs_walk_release_cache(void)
     for (int d = 0; d < MAX_DEV; ++d) {
         zs::Scratch &sc = g_scratch[d];
         std::lock_guard<std::mutex> lk(sc.mu);
-        if (!sc.p && !sc.last && !sc.pin && !sc.staged)
+        if (!sc.buf.bytes() && !sc.last && !sc.pin.bytes() && !sc.staged)
             continue;
         (void)hipSetDevice(d);
-        if (sc.p)
-            (void)hipFree(sc.p);
+        sc.buf.release();
         if (sc.last)
             (void)hipEventDestroy(sc.last);
         if (sc.staged_valid)
             (void)hipEventSynchronize(sc.staged);
-        if (sc.pin)
-            (void)hipHostFree(sc.pin);
+        sc.pin.release();
         if (sc.staged)
             (void)hipEventDestroy(sc.staged);
-        sc.p = nullptr;
-        sc.bytes = 0;
         sc.last = nullptr;
         sc.last_valid = false;
-        sc.pin = nullptr;
-        sc.pin_bytes = 0;
         sc.staged = nullptr;
         sc.staged_valid = false;
     }

@@ -1260,7 +1260,7 @@ int stage_descriptors(Scratch &sc, const zscrc_walk_image *images, size_t k, con
     if (rc)
         return rc;
     Plan p;
-    if (!plan_multi(images, k, false, 0, o, &p, static_cast<ImgD *>(sc.pin)))
+    if (!plan_multi(images, k, false, 0, o, &p, sc.pin.as<ImgD>()))
         return ZSCRC_EINVAL;
     return zs::stage_copy(sc, d_desc, bytes, s);
 }
@@ -1431,14 +1431,16 @@ int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size, const z
     /* device: descriptors, the rows, the totals, the gathered headers; host:
      * the headers, then the rows */
     const size_t desc_bytes = (k + 1) * sizeof(ImgD), rows_bytes = k * ROW * 8, hdr_bytes = k * HDR;
-    uint8_t *dfix = nullptr, *dspan = nullptr;
+    /* freed at the return, after the last synchronise: dspan, then dfix */
+    zs::ScopedBuf<zs::Device> dfix_buf, dspan;
     uint8_t *host = static_cast<uint8_t *>(malloc(rows_bytes > hdr_bytes ? rows_bytes : hdr_bytes));
     uint32_t *st = nullptr;
     uint64_t tot[ZSCRC_WALK_TOT_WORDS] = {};
     size_t cap = 0;
     int rc = host ? ZSCRC_OK : ZSCRC_ENOMEM;
-    if (!rc && hipMalloc(reinterpret_cast<void **>(&dfix), desc_bytes + rows_bytes + 64 + hdr_bytes) != hipSuccess)
-        rc = ZSCRC_ENOMEM;
+    if (!rc)
+        rc = dfix_buf.reserve(desc_bytes + rows_bytes + 64 + hdr_bytes);
+    uint8_t *const dfix = dfix_buf.as<uint8_t>();
     uint64_t *drows = reinterpret_cast<uint64_t *>(dfix + desc_bytes), *dtot = drows + k * ROW;
     uint8_t *dhdr = dfix + desc_bytes + rows_bytes + 64;
     if (!rc) {
@@ -1469,11 +1471,10 @@ int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size, const z
     uint64_t *doff = nullptr;
     uint32_t *dimg = nullptr;
     for (int pass = 0; !rc && pass < 2; ++pass) {
-        if (hipMalloc(reinterpret_cast<void **>(&dspan), cap * 28) != hipSuccess) {
-            rc = ZSCRC_ENOMEM;
+        /* the second pass frees the first one's, then allocates */
+        if ((rc = dspan.reserve(cap * 28)))
             break;
-        }
-        doff = reinterpret_cast<uint64_t *>(dspan);
+        doff = dspan.as<uint64_t>();
         dimg = reinterpret_cast<uint32_t *>(doff + 2 * cap);
         rc = zscrc_device_walk_multi(d_arena, arena_size, images, k, doff, doff + cap, dimg, cap, drows, dtot, nullptr,
                                      nullptr, 0, s);
@@ -1482,8 +1483,6 @@ int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size, const z
             rc = ZSCRC_EHIP;
         if (rc || tot[1] <= cap)
             break;
-        (void)hipFree(dspan);
-        dspan = nullptr;
         cap = (size_t)tot[1];
     }
     const size_t n = (size_t)tot[1];
@@ -1521,10 +1520,6 @@ int zscrc_device_verify_images(const void *d_arena, uint64_t arena_size, const z
                     r.first_bad++;
         }
     }
-    if (dspan)
-        (void)hipFree(dspan);
-    if (dfix)
-        (void)hipFree(dfix);
     free(st);
     free(host);
     return rc;

@@ -329,11 +329,13 @@ int zscrc_zs_verify_image(const void *image, uint64_t size, int kind, zscrc_zs_r
     rep->n_commits = n;
     rc = ZSCRC_OK;
     if (n) {
-        void *dimg = nullptr, *dmeta = nullptr;
-        hipError_t e = hipMalloc(&dimg, size);
+        /* freed at the end of this block: the image, then the descriptors */
+        zs::ScopedBuf<zs::Device> dmeta, dimg_buf;
+        hipError_t e = zs::reserve_hip(dimg_buf, size);
         if (e == hipSuccess)
-            e = hipMalloc(&dmeta, n * 24);
-        uint64_t *doff = static_cast<uint64_t *>(dmeta);
+            e = zs::reserve_hip(dmeta, n * 24);
+        void *const dimg = dimg_buf.as<void>();
+        uint64_t *doff = dmeta.as<uint64_t>();
         uint64_t *dlen = doff + n;
         uint32_t *dcrc = reinterpret_cast<uint32_t *>(dlen + n);
         uint32_t *dst = dcrc + n;
@@ -351,10 +353,6 @@ int zscrc_zs_verify_image(const void *image, uint64_t size, int kind, zscrc_zs_r
                 max_len = len[i] > max_len ? len[i] : max_len;
             rc = verify_spans(dimg, size, doff, dlen, n, max_len, dcrc, dst, nullptr, rep);
         }
-        if (dimg)
-            (void)hipFree(dimg);
-        if (dmeta)
-            (void)hipFree(dmeta);
     }
     free(off);
     free(len);
@@ -377,13 +375,11 @@ int zscrc_device_verify_image(const void *d_image, uint64_t image_size, int kind
                                          &rep->header_computed);
     /* device block of `cap` commits: offsets, lengths, CRCs, statuses (24
      * bytes a commit), then the walk's result words */
-    void *dmeta = nullptr;
+    zs::ScopedBuf<zs::Device> dmeta;
     size_t n = 0, cap = 2;
     uint64_t max_len = 0;
     int rc = ZSCRC_OK;
-    auto block = [&dmeta](size_t c) {
-        return hipMalloc(&dmeta, c * 24 + ZSCRC_WALK_RES_WORDS * 8) == hipSuccess ? ZSCRC_OK : ZSCRC_ENOMEM;
-    };
+    auto block = [&dmeta](size_t c) { return dmeta.reserve(c * 24 + ZSCRC_WALK_RES_WORDS * 8); };
     if (kind == ZSCRC_ZS_PACKED) {
         uint64_t sp[4]; /* two offsets, two lengths */
         uint64_t so[2], sl[2];
@@ -397,7 +393,7 @@ int zscrc_device_verify_image(const void *d_image, uint64_t image_size, int kind
             sp[0] = so[0], sp[1] = so[1], sp[2] = sl[0], sp[3] = sl[1];
             max_len = sl[0] > sl[1] ? sl[0] : sl[1];
             rc = block(cap);
-            if (!rc && (hipMemcpyAsync(dmeta, sp, sizeof sp, hipMemcpyHostToDevice, s) != hipSuccess ||
+            if (!rc && (hipMemcpyAsync(dmeta.as<void>(), sp, sizeof sp, hipMemcpyHostToDevice, s) != hipSuccess ||
                         hipStreamSynchronize(s) != hipSuccess))
                 rc = ZSCRC_EHIP;
         }
@@ -410,18 +406,16 @@ int zscrc_device_verify_image(const void *d_image, uint64_t image_size, int kind
         uint64_t res[ZSCRC_WALK_RES_WORDS] = {};
         cap = (size_t)(image_size / 64) + 1;
         for (int pass = 0; pass < 2; ++pass) {
-            rc = block(cap);
+            rc = block(cap); /* the second pass frees the first one's, then allocates */
             if (rc)
                 break;
-            uint64_t *doff = static_cast<uint64_t *>(dmeta), *dres = doff + 3 * cap;
+            uint64_t *doff = dmeta.as<uint64_t>(), *dres = doff + 3 * cap;
             rc = zscrc_device_walk(d_image, image_size, doff, doff + cap, cap, dres, nullptr, nullptr, 0, s);
             if (!rc && (hipMemcpyAsync(res, dres, sizeof res, hipMemcpyDeviceToHost, s) != hipSuccess ||
                         hipStreamSynchronize(s) != hipSuccess))
                 rc = ZSCRC_EHIP;
             if (rc || res[1] <= cap)
                 break;
-            (void)hipFree(dmeta);
-            dmeta = nullptr;
             cap = (size_t)res[1];
         }
         if (!rc) {
@@ -433,12 +427,10 @@ int zscrc_device_verify_image(const void *d_image, uint64_t image_size, int kind
     }
     rep->n_commits = n;
     if (!rc && n) {
-        uint64_t *doff = static_cast<uint64_t *>(dmeta);
+        uint64_t *doff = dmeta.as<uint64_t>();
         uint32_t *dcrc = reinterpret_cast<uint32_t *>(doff + 2 * cap);
         rc = verify_spans(d_image, image_size, doff, doff + cap, n, max_len, dcrc, dcrc + cap, s, rep);
     }
-    if (dmeta)
-        (void)hipFree(dmeta);
     return rc;
 }
 
