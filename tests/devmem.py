@@ -19,6 +19,37 @@ def dev_bytes(b: bytes, dev, shift: int = 0) -> torch.Tensor:
     return d
 
 
+def junk(n: int, seed: int) -> np.ndarray:
+    """n seeded pseudo-random bytes in 1..255: what surrounds the data of dev_at."""
+    return np.random.default_rng(seed).integers(1, 256, n, dtype=np.uint8)
+
+
+def dev_at(host: np.ndarray, dev, residue: int, modulus: int = 64, margin: int = 4096):
+    """(whole, view): the bytes of `host` in device memory at an address =
+    residue mod modulus, inside one allocation whose every other byte -- at
+    least `margin` on each side -- is junk() (never zero: a kernel that reads
+    before or past the data and forgets to mask it gets a wrong value, not a
+    fault and not a lucky zero).  The slice start comes from the allocation's
+    own address, whatever its alignment."""
+    assert 0 <= residue < modulus and margin > 0
+    h = np.ascontiguousarray(host).view(np.uint8).reshape(-1)
+    whole = torch.empty(h.size + 2 * margin + modulus, dtype=torch.uint8, device=dev)
+    start = margin + (residue - whole.data_ptr() - margin) % modulus
+    image = junk(whole.numel(), h.size * 31 + residue)
+    image[start:start + h.size] = h
+    whole.copy_(torch.from_numpy(image))
+    view = whole[start:start + h.size]
+    assert h.size == 0 or view.data_ptr() % modulus == residue
+    return whole, view
+
+
+def margins(whole: torch.Tensor, view: torch.Tensor):
+    """The host copies of dev_at's bytes before and after the view."""
+    start = view.storage_offset()
+    h = whole.cpu().numpy()
+    return h[:start], h[start + view.numel():]
+
+
 def dev_recs(a: np.ndarray, dev) -> torch.Tensor:
     """A host list of 32-byte entries (records, queries, gather's items) as an int64 [n, 4] device tensor."""
     return torch.from_numpy(np.ascontiguousarray(a).view(np.int64).reshape(-1, 4).copy()).to(dev)
@@ -42,6 +73,26 @@ def inside(whole: torch.Tensor, nbytes: int, what=None) -> np.ndarray:
     h = whole.cpu().numpy()
     assert bool((h[:PAD] == CANARY).all() and (h[PAD + nbytes:] == CANARY).all()), what
     return h[PAD:PAD + nbytes]
+
+
+def fenced_many(nbytes: int, k: int, dev):
+    """(whole, outs): k slices of nbytes (a multiple of 4) in one canary
+    buffer, PAD canary bytes before, between and after them."""
+    assert nbytes % 4 == 0
+    whole = torch.full((k * (nbytes + PAD) + PAD,), CANARY, dtype=torch.uint8, device=dev)
+    return whole, [whole[PAD + i * (nbytes + PAD):PAD + i * (nbytes + PAD) + nbytes] for i in range(k)]
+
+
+def inside_many(whole: torch.Tensor, nbytes: int, k: int, what=None) -> list:
+    """The host copies of fenced_many's k slices; every byte around them must hold."""
+    h = whole.cpu().numpy()
+    outs = []
+    for i in range(k + 1):
+        at = i * (nbytes + PAD)
+        assert bool((h[at:at + PAD] == CANARY).all()), (what, "fence", i)
+        if i < k:
+            outs.append(h[at + PAD:at + PAD + nbytes])
+    return outs
 
 
 def all_canary(*arrays) -> bool:

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import oracle
+from tests import devmem as dm
 from tests.golden.datagen import xorshift64_bytes
 from zeroskip_amd import device as zd
 from zeroskip_amd import crc32c as zc
@@ -23,6 +24,11 @@ M32 = 0xFFFFFFFF
 
 def to_dev(a: np.ndarray, dev) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def to_dev_at(a: np.ndarray, dev, off: int) -> torch.Tensor:
+    """The bytes at a device address = off mod 64 (a fresh upload is aligned whatever slice it came from)."""
+    return dm.dev_at(a, dev, off % 64)[1]
 
 
 def u32(t: torch.Tensor) -> np.ndarray:
@@ -67,7 +73,7 @@ def test_golden_cases_g1_walks(gpu, g1_walk):
             data = rand_bytes(stride * (n - 1) + length, stride * 7 + length)
             out = u32(zd.crc_fixed(to_dev(data, gpu), stride, length, n, seed=0x77))
             assert np.array_equal(out, _oracle_seeded(data, stride, length, n, 0x77)), (stride, length)
-            raw = u32(zd.crc_fixed(to_dev(data[3:], gpu), stride, length - 3, n - 1, raw=True))
+            raw = u32(zd.crc_fixed(to_dev_at(data[3:], gpu, 3), stride, length - 3, n - 1, raw=True))
             ref = oracle.batch(data[3:], n=n - 1, stride=stride, fixed_len=length - 3, impl="hw",
                                seeds=np.full(n - 1, M32, np.uint32)) ^ np.uint32(M32)
             assert np.array_equal(raw, ref), (stride, length, "raw")
@@ -134,7 +140,7 @@ def test_two_lane_teams(gpu, mode, shapes):
             data = rand_bytes(stride * (n - 1) + length + 3, stride * 3 + length)
             out = u32(zd.crc_fixed(to_dev(data, gpu), stride, length, n, seed=0x5a5a))
             assert np.array_equal(out, _oracle_seeded(data, stride, length, n, 0x5a5a)), (stride, length)
-            out = u32(zd.crc_fixed(to_dev(data[3:], gpu), stride, length, n, seed=7))
+            out = u32(zd.crc_fixed(to_dev_at(data[3:], gpu, 3), stride, length, n, seed=7))
             assert np.array_equal(out, _oracle_seeded(data[3:], stride, length, n, 7)), (stride, length, "+3")
     finally:
         lib().zscrc_set_small_team(0)
@@ -381,11 +387,13 @@ def test_xteam_shapes(gpu):
                                        (5, 5, 100, 1), (12345, 12000, 7, 1)]:
             data = rand_bytes(stride * (n - 1) + length + off, stride + length + n)
             assert lib().zscrc_xteam_for(length, n) == 1
-            out = u32(zd.crc_fixed(to_dev(data[off:], gpu), stride, length, n, seed=0xA5A5))
+            dd = to_dev_at(data[off:], gpu, off)
+            assert dd.data_ptr() % 64 == off
+            out = u32(zd.crc_fixed(dd, stride, length, n, seed=0xA5A5))
             ref = _oracle_seeded(data[off:], stride, length, n, 0xA5A5)
             bad = np.nonzero(out != ref)[0]
             assert bad.size == 0, (stride, length, n, off, bad[:10])
-            raw = u32(zd.crc_fixed(to_dev(data[off:], gpu), stride, length, n, seed=0x1234, raw=True))
+            raw = u32(zd.crc_fixed(dd, stride, length, n, seed=0x1234, raw=True))
             want = (~oracle.crc32c_hw(~0x1234 & M32, data[off:off + length])) & M32
             assert raw[0] == want, (stride, length, "raw")
     finally:
@@ -421,7 +429,8 @@ def test_qteam_shapes(gpu, opt, P, monkeypatch):
                                        (4100, 4097, 16390, 1), (3000, 2050, 16384, 2),
                                        (4096, 8192, 16384, 0), (0, 9000, 16386, 1)]:   # overlapping, stride 0
             data = rand_bytes(stride * (n - 1) + length + off, stride + length + n)
-            dd = to_dev(data[off:], gpu)
+            dd = to_dev_at(data[off:], gpu, off)
+            assert dd.data_ptr() % 64 == off
             name = lib().zscrc_fixed_kernel(dd.data_ptr(), stride, length, n).decode()
             names.add(name)
             assert name == ("qteam_kernel" if not opt else "qteam_dyn_kernel+qfold_kernel" if opt & QFOLD
@@ -454,7 +463,8 @@ def test_xor3_variants(gpu, qteam, opt):
     try:
         for stride, length, n, off in [(8192, 8192, 16384, 0), (12292, 12290, 16390, 3)]:
             data = rand_bytes(stride * (n - 1) + length + off, stride + n + opt)
-            dd = to_dev(data[off:], gpu)
+            dd = to_dev_at(data[off:], gpu, off)
+            assert dd.data_ptr() % 64 == off
             name = lib().zscrc_fixed_kernel(dd.data_ptr(), stride, length, n).decode()
             assert name == ("qteam_kernel" if qteam else "team_kernel<16>")
             out = u32(zd.crc_fixed(dd, stride, length, n, seed=0x5A5A))
@@ -600,7 +610,7 @@ def test_fixed_multi(gpu, stride, length, n, k):
     for b in range(k):
         h = rand_bytes(stride * (n - 1) + length + b, 1000 * b + length)[b:]
         hosts.append(h)
-        bufs.append(to_dev(h, gpu))
+        bufs.append(to_dev_at(h, gpu, b))
     before = stats()
     outs = zd.crc_fixed_multi(bufs, stride, length, n, seed=0x31337)
     if length <= 64:
